@@ -23,13 +23,17 @@ latency floor (extras.per_rank_launch_us: 8.9 us for 4 heads against 11.0 for 32
 pay before any communication — kept measurable, no longer the default.  Either way each token all-gathers
 the layers' [B, H/N*d] output slices over RCCL (`config.rccl_ranks` = what the library's communicator reports).
 
-Defaults: --steps 512 --warmup 64 (8 turns timed; ~0.2 s of GPU time + ~25 s of CPU-baseline sampling and side
-measurements); the driver may pass any K / W — the timed region always starts at a turn boundary.
+Defaults: --steps 512 --warmup 64 (8 turns timed, ~0.2 s of GPU time); the driver may pass any K / W — the timed region
+always starts at a turn boundary.  A plain run only sets up, warms up, times the K steps and prints its line; --full adds
+every side measurement (~25 s more, most of it CPU-baseline sampling).  --dump-outputs DIR writes what the last timed step
+computed (attention outputs, score stash, appended rows) as DIR/<name>.npy: the inputs are seeded, so two builds can be
+compared output for output.
 
-Prints ONE JSON line (rank 0).  `value` = whole-job tokens/s.  `roofline` describes the dominant kernel
-(decode attention, HBM-bound); `cpu_baseline` times the torch-CPU mirror of the reference's op sequence
-(oracle/torch_mirror.py — it re-`cat`s and re-rotates the whole K cache every step, as the reference does) on the host
-cores, on a bounded sample.
+Prints ONE JSON line (rank 0).  `value` = whole-job tokens/s, `ms_per_step` = milliseconds per timed step.  With --full:
+`roofline` describes the dominant kernel (decode attention, HBM-bound); `cpu_baseline` times the torch-CPU mirror of the
+reference's op sequence (oracle/torch_mirror.py — it re-`cat`s and re-rotates the whole K cache every step, as the reference
+does) on the host cores, on a bounded sample; `per_layer_launch`, `prune_event`, `comm`, `extras` and the c5 line's other
+confidence setting beside them.
 """
 import argparse
 import json
@@ -80,7 +84,7 @@ def parse():
                          "(spatten_attn_decode_chain, round 6: a workgroup walks the layers, a layer's K/V tile is requested before "
                          "the previous layer's completion is waited for; bit-identical results), 'per-layer' = one launch per "
                          "layer.  auto: chained where it applies (16-bit keys, no collective between the layers), and the "
-                         "per-layer number is measured beside it")
+                         "per-layer number is measured beside it (--full)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="c2 (default) = BASELINE.json's headline; c3 = + 25 %% head prune (configs[2]); c5 = Llama-2-13B geometry, "
                          "16384 -> 8192 rows, head prune 30 of 40, progressive quantisation k8v8 (configs[4]).  All valid at --gpus 1..8")
@@ -112,7 +116,39 @@ def parse():
                          "slices on the library-owned RCCL communicator (spatten_comm_*), captured INSIDE the token's HIP "
                          "graph; the others go through torch.distributed eagerly after the graph: one flat all-gather, the "
                          "32 per-layer all-gathers as one RCCL group, or one collective per layer")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: the per-layer launches beside the chained value, roofline, prune "
+                         "event, exchange cost, the other PQ confidence setting, the dense / eager comparison legs (unless "
+                         "--no-extras) and the CPU baseline (unless --no-cpu-baseline).  Without it a run sets up, warms up, "
+                         "times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most "
+                         "64 MB in all; rank 0's heads under head parallelism), e.g. DIR = bench_outputs")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Save each array as float32 `<name>.npy`.  When they would exceed `limit` bytes in all, the arrays above their share are
+    replaced by a fixed, seeded sample of their flattened elements (`<name>_sample.npy`) and its flat indices
+    (`<name>_sample_index.npy`, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    share = limit // max(1, len(arrays))
+    big = {k for k, a in arrays.items() if a.nbytes > share} if sum(a.nbytes for a in arrays.values()) > limit else set()
+    big_bytes = sum(arrays[k].nbytes for k in big)
+    budget = 0.95 * limit - sum(a.nbytes for k, a in arrays.items() if k not in big)     # (the others stay whole: <= share each)
+    for name, a in arrays.items():
+        if name in big:
+            k = max(1, int(a.size * budget / big_bytes / 3))            # value (4 B) + index (8 B) per sampled element
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_sample.npy"), a.reshape(-1)[idx])
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+        else:
+            np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def eager_pos_shift_layer(q, k_new, v_new, past_k, past_v, inv_freq):
@@ -700,7 +736,7 @@ def main():
         o_dense = ops.attn_decode(q[l], None, kr, Vp[l], CTX, cos, sin, CTX - 1, scores=stash_full[l].view(B, Hl, CTX), workspace=ws)
         if cfg["head_keep"]:
             head_sc.append(ops.head_scores(o_dense, Hl))                     # sum |O_h| of this rank's heads (README.md:21)
-        Krp.append(kr if headline else None)                                  # (the dense comparison legs of the headline run)
+        Krp.append(kr if headline and args.full else None)                    # (the dense comparison legs of the headline run)
         del kr
     importance = [ops.importance(s).contiguous() for s in stash_full]         # [Hl, CTX] (sum over batch, :51)
     torch.cuda.synchronize()
@@ -892,6 +928,7 @@ def main():
             if launch_mode[0] == "chained":
                 for ch in chains:
                     ch.check()
+            if launch_mode[0] == "chained" and args.full:      # (--full: the per-layer launches are timed beside it)
                 launch_mode[0] = "per-layer"
                 try:
                     graphs_per_layer = capture_slots()
@@ -930,6 +967,24 @@ def main():
     run_steps(args.warmup)
     elapsed = time_region(lambda n: run_steps(n, args.warmup), args.steps, dist_on)
     tokens_per_s = B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: every layer's attention output, the stash of scores over the rows it
+        # attended to, and the row it appended (K, its rotated shadow, V); the heads a layer did not launch are zeroed
+        slot = (base_slot + args.warmup + args.steps - 1) % TURN
+        n_last, par_last = new_len + slot + 1, slot & 1
+        torch.cuda.synchronize()
+        live = torch.ones(L, 1, Hl, 1, dtype=torch.bool, device=dev)
+        for l in range(L):
+            if hid[l] is not None:
+                live[l] = False
+                live[l, :, hid[l].long()] = True
+        host = lambda xs: torch.where(live, torch.stack(xs), 0).float().cpu().numpy()
+        write_outputs(args.dump_outputs, {
+            "attn_out": host([outs2[par_last][l].view(B, Hl, d) for l in range(L)]),                     # [L, B, H, d]
+            "scores": host([stash[l][:, :, :n_last] for l in range(L)]),                                 # [L, B, H, n]
+            "k_appended": host([Kd[l][:, :, n_last - 1] for l in range(L)]),                             # [L, B, H, d]
+            "k_rotated_appended": host([Krd[l][:, :, n_last - 1] for l in range(L)]),
+            "v_appended": host([Vd[l][:, :, n_last - 1] for l in range(L)])})
     # c5: the refetch rate of the timed run, and the OTHER confidence setting beside it (same graphs: the new rows are read through
     # fixed tensors)
     pq_side = None
@@ -938,43 +993,44 @@ def main():
         frac_of = lambda: float(sum(float(need[l][hid[l].long()].float().mean().item()) if hid[l] is not None and hid[l].numel() else
                                     float(need[l].float().mean().item()) for l in range(L)) / L)
         pq_side = {"confidence": args.pq_confidence, "refetch_fraction": round(frac_of(), 4)}
-        other = "uniform" if args.pq_confidence == "trace" else "trace"
-        for l in range(L):
-            kn[l].copy_(kn_uniform[l] if other == "uniform" else kn_trace[l])
-        run_steps(args.warmup)
-        el_o = time_region(lambda n: run_steps(n, args.warmup), args.steps, dist_on)
-        torch.cuda.synchronize()
-        pq_side.update({f"{other}_tokens_per_s": round(B * args.steps / el_o, 2), f"{other}_refetch_fraction": round(frac_of(), 4)})
-        for l in range(L):
-            kn[l].copy_(kn_trace[l] if args.pq_confidence == "trace" else kn_uniform[l])
-        # ... and the same layer-steps over 16-BIT keys and values (the lean head-list step on the rotated shadow): what MSB-first buys
-        try:
-            gb = torch.cuda.CUDAGraph()
-            nb = new_len + TURN // 2
+        if args.full:               # the other confidence setting and 16-bit keys over the same steps
+            other = "uniform" if args.pq_confidence == "trace" else "trace"
+            for l in range(L):
+                kn[l].copy_(kn_uniform[l] if other == "uniform" else kn_trace[l])
+            run_steps(args.warmup)
+            el_o = time_region(lambda n: run_steps(n, args.warmup), args.steps, dist_on)
+            torch.cuda.synchronize()
+            pq_side.update({f"{other}_tokens_per_s": round(B * args.steps / el_o, 2), f"{other}_refetch_fraction": round(frac_of(), 4)})
+            for l in range(L):
+                kn[l].copy_(kn_trace[l] if args.pq_confidence == "trace" else kn_uniform[l])
+            # ... and the same layer-steps over 16-BIT keys and values (the lean head-list step on the rotated shadow): what MSB-first buys
+            try:
+                gb = torch.cuda.CUDAGraph()
+                nb = new_len + TURN // 2
 
-            def bf16_token():
-                for l in range(L):
-                    if hid[l] is not None and hid[l].numel() == 0:
-                        continue
-                    ops.attn_decode(q[l], Kd[l], Krd[l], Vd[l], nb, cos, sin, nb - 1, k_new=kn[l], v_new=vn[l], scores=stash[l],
-                                    out=outs2[0][l], workspace=ws, head_ids=hid[l])
-            bf16_token()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(gb):
+                def bf16_token():
+                    for l in range(L):
+                        if hid[l] is not None and hid[l].numel() == 0:
+                            continue
+                        ops.attn_decode(q[l], Kd[l], Krd[l], Vd[l], nb, cos, sin, nb - 1, k_new=kn[l], v_new=vn[l], scores=stash[l],
+                                        out=outs2[0][l], workspace=ws, head_ids=hid[l])
                 bf16_token()
-            for _ in range(3):
-                gb.replay()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(30):
-                gb.replay()
-            torch.cuda.synchronize()
-            us_b = (time.perf_counter() - t0) / 30 * 1e6
-            pq_side["bf16_keys_same_steps_us_per_layer"] = round(us_b / L, 2)
-            pq_side["bf16_keys_same_steps_tokens_per_s_decode_only"] = round(1e6 / us_b, 2)
-        except Exception as e:      # noqa: BLE001
-            pq_side["bf16_keys_error"] = f"{type(e).__name__}: {e}"
-        prune()                     # (the 16-bit steps appended rows: restore the turn's start)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(gb):
+                    bf16_token()
+                for _ in range(3):
+                    gb.replay()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(30):
+                    gb.replay()
+                torch.cuda.synchronize()
+                us_b = (time.perf_counter() - t0) / 30 * 1e6
+                pq_side["bf16_keys_same_steps_us_per_layer"] = round(us_b / L, 2)
+                pq_side["bf16_keys_same_steps_tokens_per_s_decode_only"] = round(1e6 / us_b, 2)
+            except Exception as e:      # noqa: BLE001
+                pq_side["bf16_keys_error"] = f"{type(e).__name__}: {e}"
+            prune()                     # (the 16-bit steps appended rows: restore the turn's start)
     # the same K steps with one launch per layer (the r01-r05 form) beside the chained value
     tokens_per_s_per_layer = None
     if graphs_per_layer is not None:
@@ -986,7 +1042,7 @@ def main():
     # as graphs, over the same number of tokens; and — native communicator — the OTHER schedule (flat / per-layer) beside the
     # one the headline number ran, so that both are on every line (also at one rank with --force-dist)
     comm = None
-    if dist_on and native and graphs is not None:
+    if dist_on and native and graphs is not None and args.full:
         try:
             def capture(fn, slots):
                 gs = []
@@ -1066,7 +1122,7 @@ def main():
                                       "chained_over_per_layer": round(tokens_per_s / tokens_per_s_per_layer, 3),
                                       "note": "the same steps, same graphs-per-position, one launch per layer (the r01-r05 form)"}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel (decode attention, HBM-bound) -------------------------------
         # average launch duration, live: HIP events on the launch stream around replays of the 63 decode-only
         # slots; 32 launches per slot.  The figure includes the ~1 us gap between dependent launches, so it

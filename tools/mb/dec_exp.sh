@@ -12,7 +12,7 @@ for var in "$@"; do
   echo "== flags: [$var]"
   for i in 1 2; do
     if [ -n "$CMD" ]; then eval "$CMD" 2>&1 | tail -1
-    else python bench.py --steps 256 --warmup 64 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['avg_launch_us'])"
+    else python bench.py --full --steps 256 --warmup 64 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['avg_launch_us'])"
     fi
   done
 done

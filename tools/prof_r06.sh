@@ -10,14 +10,14 @@ for cfg in "c2 chained" "c2 per-layer" "c3 chained" "c5 auto"; do
   set -- $cfg
   tag=$1_$(echo $2 | tr - _)
   rm -rf $O/prof_bench_$tag
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench_$tag -o bench -- python $R/bench.py --config $1 --launch $2 --steps 256 --warmup 64 --no-cpu-baseline --no-extras > $O/prof_bench_$tag.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench_$tag -o bench -- python $R/bench.py --full --config $1 --launch $2 --steps 256 --warmup 64 --no-cpu-baseline --no-extras > $O/prof_bench_$tag.log 2>&1
   grep "^{\"metric\"" $O/prof_bench_$tag.log | tail -1 > $O/r06_bench_${tag}_line_under_rocprof.json
   python $R/tools/trim_stats.py $(find $O/prof_bench_$tag -name "*kernel_stats.csv" | head -1) $O/r06_bench_${tag}_kernel_stats.csv
   head -4 $O/r06_bench_${tag}_kernel_stats.csv | cut -c1-220
 done
 cp $O/r06_bench_c2_chained_kernel_stats.csv $O/r06_bench_kernel_stats.csv
 for cfg in c2 c3 c5; do
-  timeout 600 bash $R/tools/pmc_bench.sh $cfg > $O/pmc_bench_$cfg.log 2>&1
+  OUT=$O timeout 600 bash $R/tools/pmc_bench.sh $cfg > $O/pmc_bench_$cfg.log 2>&1
   cp $O/pmc_decode_$cfg.json $O/r06_pmc_decode_$cfg.json
   tail -1 $O/pmc_bench_$cfg.log | cut -c1-600
 done
