@@ -166,6 +166,20 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kDeferMax = 8.0f;   // natural-log units of the scaled logits
 constexpr float kSumBound = 2980.0f;   // < e^kDeferMax: a lane whose 64 exponentials sum to no more holds none above e^kDeferMax
 
+// A row whose every logit so far is a mask value (HF's finfo.min added, then rounded: all equal to the maximum) weighs those
+// keys equally, as the reference's softmax does.  Its exponent m * log2e overflows fp32 (|finfo.min| * log2e > FLT_MAX), and
+// exp2(fma(s, log2e, -m * log2e)) would be exp2(+inf): such a row takes its logits relative to m instead (s - m = 0).
+constexpr float kMaskedMax = -1.0e38f;
+template <int NKB> __device__ __forceinline__ void masked_row_shift(f32x16 (&s)[NKB], float& m_base) {
+  if (m_base < kMaskedMax) {
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[kb][r] -= m_base;     // finfo.min - m = 0, -inf stays -inf
+    m_base = 0.f;
+  }
+}
+
 template <int ROWB> __device__ inline int lds_off(int row, int slot) {
   // 16-byte slots, XOR-swizzled so the 16 lanes of a ds_read_b128 group land on distinct bank quads
   if (ROWB == 256) return row * 256 + ((slot ^ (row & 15)) << 4);
@@ -490,6 +504,7 @@ __global__ __launch_bounds__(512, 1) void prefill_pp_kernel(const FlashParams<T>
       m_tile = xor32_max(m_tile);
       m_new = fmaxf(m_run, m_tile);
       m_base = (m_new == -INFINITY) ? 0.f : m_new;  // a fully masked row: exp2(-inf) = 0 for every key
+      if (MASK) masked_row_shift(s, m_base);
     }
     const float m2 = m_base * kLog2e;
     float ls[4] = {0.f, 0.f, 0.f, 0.f};             // independent partial sums: no 32-deep dependent add chain
@@ -996,7 +1011,7 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
       }
       return xor32_max(fmaxf(fmaxf(mt[0], mt[1]), fmaxf(mt[2], mt[3]))) * (FAST && !PQK ? rsqrt_d : 1.0f);
     };
-    float m_new, lsum;                              // new running max (= the max the exponentials are taken against)
+    float m_new, lsum, m_shift;                     // new running max; the max the exponentials are taken against
     if (!MASK && !edge) {
       // fully visible tile.  Deferred rescale: the running maximum only moves (and O is only rescaled: 64 multiplies
       // per lane) when some row of the wave outgrew it by more than kDeferMax; until then P = exp(s - m_run) <=
@@ -1022,6 +1037,7 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
         if (PQK == 1) m_true = fmaxf(m_true, m_tile);
         lsum = exp_pass(m_new);
       }
+      m_shift = (m_new == -INFINITY) ? 0.f : m_new;
     } else {
       // explicit mask and / or a tile that straddles the causal diagonal: per-element visibility
       float m_tile = -INFINITY;
@@ -1039,10 +1055,13 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
       m_tile = xor32_max(m_tile);
       if (PQK == 1) m_true = fmaxf(m_true, m_tile);
       m_new = fmaxf(m_run, m_tile);
-      lsum = exp_pass((m_new == -INFINITY) ? 0.f : m_new);   // a fully masked row: exp2(-inf) = 0 for every key
+      float m_base = (m_new == -INFINITY) ? 0.f : m_new;        // a fully masked row: exp2(-inf) = 0 for every key
+      if (MASK) masked_row_shift(s, m_base);
+      lsum = exp_pass(m_base);
+      m_shift = m_base;
     }
     if (m_new != m_run) {
-      const float alpha = __expf(m_run - ((m_new == -INFINITY) ? 0.f : m_new));
+      const float alpha = __expf(m_run - m_shift);
       l_run *= alpha;
       osum[0] *= alpha;
 #pragma unroll

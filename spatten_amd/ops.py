@@ -270,6 +270,45 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     return out
 
 
+def chain_check_layers(q, k_cache, kr_cache, v_cache, out, k_new=None, v_new=None, scores=None) -> Optional[int]:
+    """Shape / dtype agreement of a chained launch's per-layer tensors (pure host logic, no device access).  Every layer's
+    k / kr / v planes are [B,H,cap,d] of one dtype, q and k_new / v_new [B,H,d], out [B,H*d], scores [B,H,rows] — all of
+    that dtype.  Returns the shortest stash row (None without a stash): a launch must not cover more rows than that."""
+    L = len(q)
+    if L == 0 or len(v_cache) != L or len(kr_cache) != L or len(out) != L or (k_cache is not None and len(k_cache) != L) \
+            or (k_new is not None and (len(k_new) != L or v_new is None or len(v_new) != L)) or (k_new is None) != (v_new is None) \
+            or (scores is not None and len(scores) != L):
+        raise ValueError("chained decode: one q / planes / out (/ k_new, v_new, scores) per layer")
+    v0 = v_cache[0]
+    if v0.dim() != 4:
+        raise ValueError("chained decode: planes are [B,H,cap,d]")
+    B, H, cap, d = v0.shape
+    dt = v0.dtype
+    for l in range(L):
+        planes = [kr_cache[l], v_cache[l]] + ([k_cache[l]] if k_cache is not None else [])
+        if any(t.shape != v0.shape or t.dtype != dt for t in planes):
+            raise ValueError(f"chained decode: layer {l}: k / kr / v planes must all be [B,H,cap,d] = {tuple(v0.shape)} of {dt}")
+        if q[l].shape != (B, H, d) or q[l].dtype != dt:
+            raise ValueError(f"chained decode: layer {l}: q must be [B,H,d] = {(B, H, d)} of {dt}")
+        if k_new is not None and any(t.shape != (B, H, d) or t.dtype != dt for t in (k_new[l], v_new[l])):
+            raise ValueError(f"chained decode: layer {l}: k_new / v_new must be [B,H,d] = {(B, H, d)} of {dt}")
+        if out[l].shape != (B, H * d) or out[l].dtype != dt:
+            raise ValueError(f"chained decode: layer {l}: out must be [B,H*d] = {(B, H * d)} of {dt}")
+        if scores is not None and (scores[l].dim() != 3 or scores[l].shape[:2] != (B, H) or scores[l].dtype != dt):
+            raise ValueError(f"chained decode: layer {l}: scores must be [B,H,rows] of {dt}")
+    return None if scores is None else min(int(s.shape[2]) for s in scores)
+
+
+def chain_check_stash(stash_rows: Optional[int], kv_len: int, device_length: bool, layout: int = 0):
+    """A chained token writes stash rows below ``kv_len`` (the static length, or the BOUND of the device-length form; that
+    form also refuses a layout beyond the shortest row)."""
+    if stash_rows is None:
+        return
+    need = max(int(kv_len), int(layout)) if device_length else int(kv_len)
+    if need > stash_rows:
+        raise ValueError(f"chained decode: a stash row holds {stash_rows} entries, the launch covers {need}")
+
+
 class DecodeChain:
     """The attention step of ALL layers of one decode token as ONE launch (``spatten_attn_decode_chain``, include/spatten.h
     ABI 5): what the caller's layer loop issues as one ``attn_decode`` per LlamaAttention module (modify_llama.py:86-147).
@@ -280,7 +319,10 @@ class DecodeChain:
     [B,H,>=kv_len] or None, ``head_ids`` per layer: int32 tensor (possibly empty) or None.  MHA, bf16 / f16, d = 128."""
 
     def __init__(self, q, k_cache, kr_cache, v_cache, out, k_new=None, v_new=None, scores=None, head_ids=None,
-                 max_splits: int = 16, depth: int = 0):
+                 max_splits: Optional[int] = None, depth: int = 0):
+        # max_splits (default): every count decode_auto_splits picks up to the capacity — it grows to max(16, rows / 256) for a
+        # few heads over long rows, e.g. 32 at 8190 rows — within the per-layer launch's bound (DecodeWorkspace)
+        self.stash_rows = chain_check_layers(q, k_cache, kr_cache, v_cache, out, k_new, v_new, scores)
         L = len(q)
         lib = _lib.load()
         v0 = v_cache[0]
@@ -328,6 +370,8 @@ class DecodeChain:
         self.new_sb, self.new_sh = (k_new[0].stride(0), k_new[0].stride(1)) if self.append else (0, 0)
         self.out_sb = out[0].stride(0)
         self.sc_sb, self.sc_sh = (scores[0].stride(0), scores[0].stride(1)) if scores is not None else (0, 0)
+        if max_splits is None:
+            max_splits = min(_lib.DECODE_MAX_SPLITS, max(16, lib.spatten_decode_auto_splits(B, 1, d, cap)))
         self.max_splits, self.depth = max_splits, depth
         self.ws = torch.zeros(lib.spatten_decode_chain_workspace_bytes(L, B, H, d, max_splits), dtype=torch.uint8, device=v0.device)
 
@@ -342,6 +386,7 @@ class DecodeChain:
         _dev(cos, sin)
         if kv_len > self.cap or (step is None and max(kv_len, pos_q + 1) > cos.shape[0]) or cos.shape[1] * 2 != self.d or (step is not None and layout > self.cap):
             raise ValueError("kv_len exceeds cache capacity or rotary table")
+        chain_check_stash(self.stash_rows, kv_len, step is not None, layout)
         a = _lib.ChainArgs()
         a.struct_size = ctypes.sizeof(_lib.ChainArgs)
         a.dtype = self.dtype

@@ -194,3 +194,37 @@ def test_chain_unsupported_shapes_are_refused_not_run():
                          [mk(B, H, cap, d) for _ in range(L)], [mk(B, H * d) for _ in range(L)])
     with pytest.raises(NotImplementedError):
         ch(100, cos, sin, 99)               # head_dim 64 is not instantiated
+
+
+@pytest.mark.parametrize("H", [4, 8])
+def test_chain_few_heads_over_c5_rows_fit_the_split_workspace(H):
+    # a head-parallel rank of 4 / 8 heads over 8190 rows: decode_auto_splits gives up to max(16, rows / 256) = 32 splits, more
+    # than the chain's workspace held before it was sized like the per-layer one — the chain must run, bit for bit
+    _run_pair(2, 1, H, 128, 8189, 8320, "bf16", steps=2)
+
+
+def test_chain_refuses_a_stash_shorter_than_the_launch():
+    """The stash length, out shape and per-layer dtype are validated in Python; nothing is launched on a short buffer."""
+    from spatten_amd import ops
+    tdt = torch.bfloat16
+    L, B, H, d, cap = 2, 1, 4, 128, 512
+    cos, sin = ops.rope_table(cap + 8, d, tdt, "cuda")
+    mk = lambda *s, dt=tdt: torch.zeros(*s, dtype=dt, device="cuda")
+    planes = lambda: [mk(B, H, cap, d) for _ in range(L)]
+    q, kn, vn = [mk(B, H, d) for _ in range(L)], [mk(B, H, d) for _ in range(L)], [mk(B, H, d) for _ in range(L)]
+    outs = [mk(B, H * d) for _ in range(L)]
+    st = [mk(B, H, cap), mk(B, H, cap)[:, :, :300]]     # layer 1's stash holds 300 rows (same strides)
+    ch = ops.DecodeChain(q, planes(), planes(), planes(), outs, k_new=kn, v_new=vn, scores=st)
+    with pytest.raises(ValueError):
+        ch(301, cos, sin, 300)
+    step = ops.StepState(cos, sin)
+    step.set(200, 199)
+    with pytest.raises(ValueError):
+        ch(cap, cos, sin, 0, step=step)                 # the device-length form: the bound must fit every stash
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError):                     # out is not [B, H*d]
+        ops.DecodeChain(q, planes(), planes(), planes(), [mk(B, H * d), mk(B, H * d // 2)], k_new=kn, v_new=vn)
+    with pytest.raises(ValueError):                     # layers of mixed dtypes
+        ops.DecodeChain(q, planes(), planes(), [mk(B, H, cap, d), mk(B, H, cap, d, dt=torch.float16)], outs, k_new=kn, v_new=vn)
+    with pytest.raises(ValueError):                     # k_new of another shape
+        ops.DecodeChain(q, planes(), planes(), planes(), outs, k_new=[kn[0], mk(B, H - 1, d)], v_new=vn)
