@@ -650,6 +650,44 @@ typedef struct spatten_pq_decode_args {
 } spatten_pq_decode_args_t;
 int spatten_attn_decode_pq(const spatten_pq_decode_args_t* args, void* stream);
 
+/* The whole SpAtten cascade of one decode step over the planes (parity unpinned; SpAttenController.scala:402,546-558,591-612;
+ * RequantDecision.scala:44-72): MSB scores, LSB refetch for the flagged heads, local V pruning, cumulative token importance.
+ * Four dependent launches: the MSB pass and the refetch pass in SCORES-ONLY form (no V traffic: the stash, lse, need_lsb and the
+ * final fp32 logits — msb_logit holds them after the call), the kept-row select (per launched head the `keep` largest stash
+ * entries, ties lowest index first — TopK.scala:193-212), and the P.V gather over only the kept rows of the quantised V plane:
+ * out[b,h] = sum over kept j of exp(logit_j - lse_max) / lse_sum * qv_j * val_scale_j (full-row probabilities of the final fp32
+ * logits, no renormalisation).
+ *   step            the step exactly as spatten_attn_decode_pq takes it (step.struct_size = sizeof(spatten_pq_decode_args_t));
+ *                   scores, lse and out required, flags 0; the append inside the MSB pass (k_new ...) works as there
+ *   keep            kept rows per head (host form), clamped to [1, kv_len]
+ *   keep_fraction   with step.step_state: the kept count is ceil(keep_fraction * length) in fp64 on the device (the bound
+ *                   = step.kv_len sizes the launches), clamped to [1, length]; (0, 1].  Host form: 0, or the fraction `keep`
+ *                   came from — the gather is then laid out for ceil(keep_fraction * kv_len_layout) rows like the device-length
+ *                   form of the same layout: the two give bit-identical outputs
+ *   importance_acc  optional cascade importance (README.md:11), fused and deferred by one step like spatten_decode_args_t's: while
+ *                   the MSB pass streams the keys, acc[h, j] += exp(logit_prev_j - prev_lse[unit, 0]) / prev_lse[unit, 1] for
+ *                   j < prev_len (step_state: state word 3), where logit_prev is the PREVIOUS step's final fp32 logit still in
+ *                   msb_logit and prev_lse its (max, sum) — the gather copies each launched unit's lse there at the end of the
+ *                   step, so the caller keeps ONE pair of buffers.  acc [H, >= kv_len] fp32, stride acc_sh.  The last step
+ *                   before a prune is folded with spatten_importance_accumulate(SPATTEN_F32, msb_logit, lse).
+ *   workspace       spatten_pq_local_v_workspace_bytes(batch, heads, head_dim, workspace_rows) bytes, zero-filled once, one
+ *                   per stream, re-armed by the kernels; workspace_rows >= step.kv_len.  Layout: arrival counters (uint32
+ *                   [batch*heads], padded to 256 bytes) | gather partials (fp32 [batch*heads, 64, head_dim]) | kept lists (int32
+ *                   [batch*heads, workspace_rows]: after the call, row b*heads+h of a launched head holds its kept positions,
+ *                   ascending)
+ * Pruned heads (step.head_ids) are not launched in any pass; their rows of out / stash / lse are left untouched. */
+typedef struct spatten_pq_local_v_args {
+  uint32_t struct_size;            /* sizeof(spatten_pq_local_v_args_t) of the caller */
+  int32_t keep;
+  spatten_pq_decode_args_t step;
+  double keep_fraction;
+  float* importance_acc; int64_t acc_sh;
+  float* prev_lse; int32_t prev_len; int32_t workspace_rows;
+  void* workspace;
+} spatten_pq_local_v_args_t;
+size_t spatten_pq_local_v_workspace_bytes(int batch, int heads, int head_dim, int max_kv_len);
+int spatten_attn_decode_pq_local_v(const spatten_pq_local_v_args_t* args, void* stream);
+
 /* Prefill over the planes (BASELINE.json configs[3]: prefill + progressive quantisation).  Same query / value / output /
  * mask / position arguments as spatten_attn_prefill; the keys come from the MSB / LSB planes: pass 1 scores every query
  * row from the MSB plane (logits in fp32), need_lsb[b,h,i] = (max_j prob_ij < threshold) per QUERY ROW (int32 [B,H,q_len],

@@ -12,6 +12,13 @@ step's stashed scores, prefill the prompt, greedy-decode ``max_gen_len`` tokens}
     python run_spatten_synthetic.py --layers 12 --schedule tests/golden/trace_synthetic.csv      # per-layer keeps from a trace
     python run_spatten_synthetic.py --prompts tests/golden/mt_bench_sample.jsonl                 # MT-Bench turn structure
     python run_spatten_synthetic.py --trace tests/golden/trace_synthetic.csv --kv-len 4096     # cascade schedule demo, one K/V pair
+    python run_spatten_synthetic.py --schedule tests/golden/trace_full_cascade.csv --full-cascade --pq-threshold 0.05
+    python run_spatten_synthetic.py --trace tests/golden/trace_full_cascade.csv --pq --full-cascade --pq-threshold 0.05
+
+``--full-cascade`` turns on everything such a trace carries at once — the bit profile with the LSB refetch, local V pruning at
+the trace's value fraction, cumulative importance where ``if_accumulate_importance`` is set — as the composed step over the
+quantised planes (spatten_attn_decode_pq_local_v).  A trace that quantises its keys without a threshold (``auto_requant_thres``
+-1: the RTL harness forces the requant on, spatten_amd/traces.py) takes it from ``--pq-threshold``.
 
 ``--trace`` reads a schedule in the format of the reference's ``spatten_hardware/hardware/workloads/*.csv``
 (spatten_amd/traces.py) and applies its per-layer token / local-V / head keep ratios and requant threshold to one
@@ -91,6 +98,72 @@ def greedy_generate(model, input_ids, past_key_values, max_gen_len):          # 
     return past_key_values, len(generated), (max_gen_len - 1) / max(time.perf_counter() - t0, 1e-9)
 
 
+def full_cascade_options(sched, pq_threshold=None, iteration: int = 0):
+    """--full-cascade: the trace's value fraction -> local_v_keep (values / keys over all layers), if_accumulate_importance ->
+    importance_mode="cascade", its bit profile -> pq_profile, its requant threshold (or ``pq_threshold`` where the trace has
+    none) -> pq_threshold.  Returns the enable_spatten_llm keywords."""
+    from spatten_amd import ops
+    steps = sched.layers(iteration)
+    prof = sched.pq_profile(iteration)
+    if prof not in ops.PQ_PROFILES:
+        raise SystemExit(f"--full-cascade: the trace's bit profile {prof} is not one of {ops.PQ_PROFILES}")
+    thr = [s.requant_threshold for s in steps if s.requant and s.requant_threshold >= 0]
+    if thr:
+        threshold = float(thr[0]) if pq_threshold is None else float(pq_threshold)
+    elif pq_threshold is None:
+        raise SystemExit("--full-cascade: the trace quantises its keys but carries no requant threshold "
+                         "(auto_requant_thres -1): pass --pq-threshold")
+    else:
+        threshold = float(pq_threshold)
+    keys = sum(s.keys for s in steps)
+    local_v = min(1.0, max(1e-3, round(sum(s.values for s in steps) / max(keys, 1), 4)))
+    ext = {"pq_profile": prof, "pq_threshold": threshold, "local_v_keep": local_v}
+    if any(s.accumulate_importance for s in steps):
+        ext["importance_mode"] = "cascade"
+    return ext
+
+
+def schedule_options(args):
+    """--schedule: per-layer schedule in the reference's workloads/*.csv format (spatten_amd/traces.py): the token keep ratios
+    become layer_keep (layer-to-layer cascade), the head ratios head_keep, the requant threshold pq_threshold (with
+    --full-cascade: the whole composed step, full_cascade_options)."""
+    from spatten_amd.traces import read_trace
+    ext = {}
+    sched = read_trace(args.schedule)
+    fr = sched.fractions(0)
+    if sched.token_scope(0) == "global":      # one key_fetch_num per layer for all heads: ONE kept set per layer
+        ext["token_scope"] = "global"
+    fr = [fr[min(i * len(fr) // args.layers, len(fr) - 1)] for i in range(args.layers)]      # stretch to our depth
+    top = max(f["token_keep"] for f in fr)
+    keeps, heads = [], []
+    for f in fr:
+        keeps.append(max(8, min(args.important_size, int(round(args.important_size * f["token_keep"] / top)))))
+        heads.append(max(1, int(round(args.heads * f["head_keep"]))))
+    ext["layer_keep"] = [min(keeps[:i + 1]) for i in range(len(keeps))]
+    if min(heads) < args.heads:
+        ext["head_keep"] = [min(heads[:i + 1]) for i in range(len(heads))]
+    if getattr(args, "full_cascade", False):
+        ext.update(full_cascade_options(sched, args.pq_threshold))
+        return ext
+    thr = [f["requant_threshold"] for f in fr if f["requant_threshold"] is not None]
+    if thr and args.pq_threshold is None and args.local_v_keep is None:
+        ext["pq_threshold"] = float(thr[0])
+        prof = sched.pq_profile(0)         # the trace's bit columns: key MSB bits / value bits
+        if prof in ((4, 8), (8, 8), (6, 6)) and not args.cascade:
+            ext["pq_profile"] = prof
+    return ext
+
+
+def print_full_cascade_layers(ext, layers, heads):
+    """Per layer: kept keys (important tokens), values fetched per step (ceil(local_v_keep x keys)), heads, profile."""
+    import math
+    print(f"{'layer':>5} {'keys':>6} {'values':>6} {'heads':>5} {'profile':>8}")
+    hk = ext.get("head_keep") or [heads] * layers
+    for l in range(layers):
+        k = ext["layer_keep"][l]
+        print(f"{l:>5} {k:>6} {math.ceil(ext['local_v_keep'] * k):>6} {hk[l]:>5} {str(tuple(ext['pq_profile'])):>8}")
+
+
 def chat(args):
     from spatten_amd import enable_spatten_llm
     dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[args.dtype]
@@ -106,29 +179,10 @@ def chat(args):
     if args.local_v_keep is not None:
         ext["local_v_keep"] = args.local_v_keep
     if args.schedule:
-        # per-layer schedule in the reference's workloads/*.csv format (spatten_amd/traces.py): the token keep ratios
-        # become layer_keep (layer-to-layer cascade), the head ratios head_keep, the requant threshold pq_threshold
-        from spatten_amd.traces import read_trace
-        sched = read_trace(args.schedule)
-        fr = sched.fractions(0)
-        if sched.token_scope(0) == "global":      # one key_fetch_num per layer for all heads: ONE kept set per layer
-            ext["token_scope"] = "global"
-        fr = [fr[min(i * len(fr) // args.layers, len(fr) - 1)] for i in range(args.layers)]      # stretch to our depth
-        top = max(f["token_keep"] for f in fr)
-        keeps, heads = [], []
-        for f in fr:
-            keeps.append(max(8, min(args.important_size, int(round(args.important_size * f["token_keep"] / top)))))
-            heads.append(max(1, int(round(args.heads * f["head_keep"]))))
-        ext["layer_keep"] = [min(keeps[:i + 1]) for i in range(len(keeps))]
-        if min(heads) < args.heads:
-            ext["head_keep"] = [min(heads[:i + 1]) for i in range(len(heads))]
-        thr = [f["requant_threshold"] for f in fr if f["requant_threshold"] is not None]
-        if thr and args.pq_threshold is None and args.local_v_keep is None:
-            ext["pq_threshold"] = float(thr[0])
-            prof = read_trace(args.schedule).pq_profile(0)         # the trace's bit columns: key MSB bits / value bits
-            if prof in ((4, 8), (8, 8), (6, 6)) and not args.cascade:
-                ext["pq_profile"] = prof
+        ext.update(schedule_options(args))
         print("schedule:", {k: v for k, v in ext.items()})
+        if args.full_cascade:
+            print_full_cascade_layers(ext, args.layers, args.heads)
     if args.auto_graph:       # the loop below stays the reference's: its single-token calls replay one captured graph per token
         ext.update(auto_graph=True, fuse_qkv=True, native_gemv=True)
     kv_cache = enable_spatten_llm(model, args.start_size, args.important_size, args.recent_size, **ext)     # :110-115
@@ -175,6 +229,9 @@ def cascade(args):
     sched = read_trace(args.trace)
     fr = sched.fractions(0)
     prof = sched.pq_profile(0)            # (key MSB bits, value bits) of the trace, TestSpAtten.scala:64-97
+    full = full_cascade_options(sched, args.pq_threshold) if args.full_cascade else None
+    if full is not None and not args.pq:
+        raise SystemExit("--trace --full-cascade runs the quantised planes: add --pq")
     dt, H, d, N = torch.bfloat16, args.heads, args.head_dim, args.kv_len
     gen = torch.Generator(device="cuda").manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=gen).to(dt)
@@ -187,8 +244,8 @@ def cascade(args):
     stash = torch.empty(1, H, N, dtype=dt, device="cuda")
     lse = torch.empty(1, H, 2, dtype=torch.float32, device="cuda")
     n = N
-    print(f"{'layer':>5} {'keys':>6} {'values':>6} {'heads':>5} {'pq_thr':>6} {'us':>8}")
-    for f in fr:
+    print(f"{'layer':>5} {'keys':>6} {'values':>6} {'heads':>5} {'pq_thr':>6} {'us':>8}" + ("  profile" if full else ""))
+    for f, step in zip(fr, sched.layers(0)):
         keep = max(int(round(f["token_keep"] * N)), 16)
         if keep < n:                                  # global token pruning on the ACCUMULATED importance
             idx = ci.select(0, n, 4, n, keep - 4)
@@ -200,7 +257,21 @@ def cascade(args):
         vkeep = max(int(round(f["value_keep"] * n)), 1)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        if f["requant_threshold"] is not None and args.pq and prof in ops.PQ_PROFILES:
+        # a layer requants where the trace says so, or where it quantises its keys at a width the harness runs as 8 bits with
+        # the requant forced on (-1 / 10 / 12, spatten_amd/traces.py)
+        requant = f["requant_threshold"] is not None or step.key_bits in (-1, 10, 12)
+        composed = full is not None and requant and vkeep < n
+        if composed:
+            # the composed step (spatten_attn_decode_pq_local_v): MSB scores, LSB refetch below the threshold, V only for the
+            # vkeep most probable keys and only from the quantised V plane; the step's probabilities feed the importance
+            f = dict(f, requant_threshold=full["pq_threshold"])
+            planes = ops.PQProfilePlanes(1, H, H, n, d, "cuda", key_bits=prof[0], value_bits=prof[1])
+            ops.pq_pack_planes(Kr, V, planes, 0, n)
+            out = ops.attn_decode_pq_local_v(q, planes, n, cos, sin, n - 1, full["pq_threshold"], vkeep, stash, lse,
+                                             head_ids=heads)
+            if heads is not None:
+                out.view(1, H, d)[:, [h for h in range(H) if h not in set(heads.tolist())]] = 0
+        elif f["requant_threshold"] is not None and args.pq and prof in ops.PQ_PROFILES:
             # the trace's bit profile: quantised value plane, LSB-only refetch (ops.PQProfilePlanes)
             planes = ops.PQProfilePlanes(1, H, H, n, d, "cuda", key_bits=prof[0], value_bits=prof[1])
             ops.pq_pack_planes(Kr, V, planes, 0, n)
@@ -218,11 +289,15 @@ def cascade(args):
             out = ops.attn_decode(q, None, Kr, V, n, cos, sin, n - 1, scores=stash, lse=lse, head_ids=heads)
         torch.cuda.synchronize()
         us = (time.perf_counter() - t0) * 1e6
-        ci.accumulate(0, stash[:, :, None, :], lse[:, :, None, :])
+        if composed:       # the final fp32 logits the step's probabilities come from
+            ci.accumulate(0, planes.msb_logit[:, :, None, :n], lse[:, :, None, :])
+        else:
+            ci.accumulate(0, stash[:, :, None, :], lse[:, :, None, :])
         hp.observe(torch.nan_to_num(out)[:, None, :])
         q = rnd(1, H, d)
         thr = f["requant_threshold"]
-        print(f"{f['layer']:>5} {n:>6} {vkeep:>6} {H if heads is None else heads.numel():>5} {('-' if thr is None else thr):>6} {us:>8.1f}")
+        print(f"{f['layer']:>5} {n:>6} {vkeep:>6} {H if heads is None else heads.numel():>5} {('-' if thr is None else thr):>6} {us:>8.1f}"
+              + (f"  {tuple(prof)}" if full else ""))
 
 
 def main():
@@ -249,7 +324,11 @@ def main():
     ap.add_argument("--trace", default=None, help="cascade schedule CSV (format of the reference's workloads/*.csv)")
     ap.add_argument("--kv-len", type=int, default=4096)
     ap.add_argument("--pq", action="store_true", help="--trace: use progressive-quant keys where the trace requants")
+    ap.add_argument("--full-cascade", action="store_true", help="--schedule / --trace --pq: the composed step over the quantised "
+                    "planes (bit profile + LSB refetch + local V at the trace's value fraction + cumulative importance)")
     args = ap.parse_args()
+    if args.full_cascade and not (args.schedule or args.trace):
+        raise SystemExit("--full-cascade applies to --schedule or --trace")
     if not torch.cuda.is_available():
         raise SystemExit("run_spatten_synthetic.py needs the MI355X (there is no CPU path in the product)")
     cascade(args) if args.trace else chat(args)

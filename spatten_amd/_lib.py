@@ -104,6 +104,18 @@ class PQDecodeArgs(ctypes.Structure):
     ]
 
 
+
+class PQLocalVArgs(ctypes.Structure):
+    """``spatten_pq_local_v_args_t`` (include/spatten.h): the profiled step + local V pruning + cascade importance."""
+    _fields_ = [
+        ("struct_size", c_uint32), ("keep", c_int32),
+        ("step", PQDecodeArgs),
+        ("keep_fraction", ctypes.c_double),
+        ("importance_acc", c_void_p), ("acc_sh", c_int64),
+        ("prev_lse", c_void_p), ("prev_len", c_int32), ("workspace_rows", c_int32),
+        ("workspace", c_void_p),
+    ]
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libspatten_hip.so")
 if os.environ.get("SPATTEN_LIB"):          # developer A/B: a variant build of the library (tools/mb/build_variant.sh)
@@ -190,6 +202,10 @@ def _declare(lib):
     lib.spatten_kv_append_planes.argtypes = [i, p, p, i64, i64, p, p, p, i64, i64, POINTER(PQPlanesDesc), p, p, i, i, i, i, i, i, p, p]
     lib.spatten_attn_decode_pq.restype = c_int
     lib.spatten_attn_decode_pq.argtypes = [POINTER(PQDecodeArgs), p]
+    lib.spatten_pq_local_v_workspace_bytes.restype = c_size_t
+    lib.spatten_pq_local_v_workspace_bytes.argtypes = [i, i, i, i]
+    lib.spatten_attn_decode_pq_local_v.restype = c_int
+    lib.spatten_attn_decode_pq_local_v.argtypes = [POINTER(PQLocalVArgs), p]
     lib.spatten_prefill_workspace_bytes.restype = c_size_t
     lib.spatten_prefill_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
     lib.spatten_attn_prefill.restype = c_int

@@ -27,9 +27,11 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "common.h"
 #include "pq_pack.h"
+#include "select_row.h"
 
 namespace spatten {
 
@@ -53,6 +55,10 @@ struct PqvParams {
   // (every workgroup derives the list itself from `need`: one wave load + ballot, no counter to reset), S / chunk of this pass are
   // its own — many short splits, so that two or three flagged heads are spread over the chip instead of over 8 CUs each
   int compact, n_act, S1, chunk1;                // (S1 / chunk1: pass 1's layout, taken when most heads are flagged)
+  // the SCORES-ONLY form (SO: local V pruning over the planes, spatten_attn_decode_pq_local_v): the MSB pass folds the previous
+  // step's probabilities into acc[h, j] (j < prev_len; DYN: state word 3) from the fp32 logits that step left in msb_logit and its
+  // (max, sum) in prev_lse — read before this pass overwrites the row, by the thread that overwrites it
+  float* acc; int64_t acc_sh; const float* prev_lse; int prev_len;
 };
 
 #ifndef SPATTEN_PQV_UP
@@ -175,7 +181,9 @@ template <int BITS, int W> __device__ inline void fma_piece(float (&o)[16], cons
 // APP (round 5): the MSB pass that also appends the step's row — its own instantiation: carried as a run-time branch the path cost every
 // OTHER caller 0.8-1.0 us per pass (a branch around the new token's loads behind the first tile breaks the exact vmcnt the
 // pipelined tiles rely on: same-call A/B, (4,8) 15.5 vs 14.65 us).
-template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false>
+// SO (scores only): no V traffic and no output — the stash, the fp32 logits (msb_logit: pass 1 all heads, the refetch pass
+// rewrites the flagged heads' rows with their final logits), lse and need_lsb; the kept-row select and the gather follow
+template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false>
 __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams<T> p_in) {
   PqvParams<T> p = p_in;                         // (the compact refetch pass picks its split layout by the number of flagged heads)
   constexpr int LPR = D / 16;                    // lanes per row: lane c owns the row's piece c (16 elements)
@@ -226,8 +234,15 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   const int unit = b * p.H + h;
   if (PASS == 2 && p.need[unit] == 0) return;    // confident head: pass 1 already produced its output
 
-  int n_dyn = 0;
+  int n_dyn = 0, pl_dyn = 0;
   if (DYN) n_dyn = p.step[opaque_lane(0)];       // requested FIRST (in-order returns), read after the tile loads went out
+  constexpr bool fold = SO && PASS == 1;         // (the cascade fold: prev_len = 0 / acc == NULL turn it off at run time)
+  float prev_ml[2] = {0.f, 1.f};
+  if (fold) {
+    if (DYN) pl_dyn = p.step[3 + opaque_lane(0)];
+    const float* ml = p.prev_lse + 2 * unit + opaque_lane(0);
+    prev_ml[0] = ml[0]; prev_ml[1] = ml[1];
+  }
   const int lo = split * p.chunk;
   const int rl = min(lo + p.chunk, p.N);         // static row limit of the loads (DYN: p.N is the bound): rows >= rl read as 0
 
@@ -237,7 +252,8 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   const __amdgpu_buffer_rsrc_t rs_ks = make_rsrc(p.pl.ks + b * p.pl.sc_sb + hkv * p.pl.sc_sh, (int64_t)rl * 4);
   const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(p.pl.vq + b * p.pl.vq_sb + hkv * p.pl.vq_sh, (int64_t)rl * VROW);
   const __amdgpu_buffer_rsrc_t rs_vs = make_rsrc(p.pl.vs + b * p.pl.sc_sb + hkv * p.pl.sc_sh, (int64_t)rl * 4);
-  const __amdgpu_buffer_rsrc_t rs_lg = make_rsrc(lgb, (int64_t)rl * 4);
+  // (the fold's old logits: a descriptor of 0 records when nothing is folded — the loads then touch no memory)
+  const __amdgpu_buffer_rsrc_t rs_lg = make_rsrc(lgb, (PASS == 2 || (fold && p.acc != nullptr)) ? (int64_t)rl * 4 : 0);
   // Rows of a tile (round 5): thread-row r owns the UP CONSECUTIVE rows t0 + r UP + u (r04: t0 + u RPI + r) — a wave's rows of a
   // tile are then one contiguous run, the UP row scales of a lane are ONE 16-byte load per plane (r04: a 4-byte load per
   // row-group and plane — half of the kernel's memory instructions carried 32 bytes per wave), and a lane's UP stash entries /
@@ -248,17 +264,19 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   struct Tile {
     uint32_t kw[UP][KW]; uint32_t ks[UP];        // this lane's piece of the key row + the rows' scales (fp32 bits)
     uint32_t vw[UP][VW]; uint32_t vs[UP];
-    uint32_t lg[UP];                             // PASS 2: the MSB logits pass 1 left
+    uint32_t lg[UP];                             // PASS 2: the MSB logits pass 1 left; SO pass 1: the previous step's logits
   };
   Tile tile_a, tile_b;
   auto issue = [&](Tile& tl, int t0) {
     bload<UP>(rs_ks, vo_s, t0 * 4, tl.ks);
-    if (PASS == 2) bload<UP>(rs_lg, vo_s, t0 * 4, tl.lg);
+    if (PASS == 2 || fold) bload<UP>(rs_lg, vo_s, t0 * 4, tl.lg);
 #pragma unroll
     for (int u = 0; u < UP; ++u) bload<KW>(rs_k, vo_k, (t0 + u) * KROW, tl.kw[u]);   // (wave-uniform part in the scalar offset)
-    bload<UP>(rs_vs, vo_s, t0 * 4, tl.vs);
+    if (!SO) {
+      bload<UP>(rs_vs, vo_s, t0 * 4, tl.vs);
 #pragma unroll
-    for (int u = 0; u < UP; ++u) bload<VW>(rs_v, vo_v, (t0 + u) * VROW, tl.vw[u]);
+      for (int u = 0; u < UP; ++u) bload<VW>(rs_v, vo_v, (t0 + u) * VROW, tl.vw[u]);
+    }
   };
 
   typename V8::raw q_raw[4];
@@ -320,7 +338,12 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   // the bounds check) and whose per-lane offset is out of range for every lane but the row's first (c != 0)
   T* stashp = p.scores ? p.scores + b * p.sc_sb + h * p.sc_sh : nullptr;
   const __amdgpu_buffer_rsrc_t rs_st = make_rsrc(stashp, stashp ? (int64_t)hi * (int64_t)sizeof(T) : 0);
-  const __amdgpu_buffer_rsrc_t rs_lgw = make_rsrc(lgb, PASS == 1 ? (int64_t)hi * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rs_lgw = make_rsrc(lgb, (PASS == 1 || SO) ? (int64_t)hi * 4 : 0);
+  const int prev_len = !fold ? 0 : (p.acc == nullptr) ? 0 : DYN ? __builtin_amdgcn_readfirstlane(pl_dyn) : p.prev_len;
+  float* accp = (fold && p.acc != nullptr) ? p.acc + h * p.acc_sh : nullptr;
+  // (exp / sum with a true division: the same bits as spatten_importance_accumulate's fold of the same row, so a step folded
+  //  here and a step folded by the flush add identical values — an eager loop and a graph that binds mid-turn agree)
+  const float casc_m = (prev_ml[0] == -INFINITY) ? 0.f : prev_ml[0], casc_l = prev_ml[1];
   const int vo_st = (c == 0) ? r * (UP * (int)sizeof(T)) : 0x40000000, vo_lw = (c == 0) ? r * (UP * 4) : 0x40000000;
 
   float m_run = -INFINITY, l_run = 0.f, off_run = 0.f;
@@ -361,9 +384,11 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
         lgb[N - 1] = sn;
       }
       m_run = sn; l_run = 1.f;                           // the first key of this thread-row's softmax
-      const float wgt = pp.vs;
-      fma_piece<VB, VW>(o16, pp.wv, wgt);
-      off_run = wgt;
+      if (!SO) {
+        const float wgt = pp.vs;
+        fma_piece<VB, VW>(o16, pp.wv, wgt);
+        off_run = wgt;
+      }
     }
   }
   // every row-group of a tile is computed unconditionally (rows past the split read as zeros); `valid` gates the results
@@ -382,6 +407,13 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       const float s = a * (__uint_as_float(tl.ks[u]) * (PASS == 1 ? 16.f * rsqrt_d : rsqrt_d));
       sc[u] = (PASS == 2) ? s + __uint_as_float(tl.lg[u]) : s;
     }
+    if (fold && c == 0) {        // the previous step's probability of key j, before this pass overwrites its logit
+#pragma unroll
+      for (int u = 0; u < UP; ++u) {
+        const int j = t0 + r * UP + u;
+        if (j < prev_len && j < hi) atomicAdd(accp + j, __expf(__uint_as_float(tl.lg[u]) - casc_m) / casc_l);
+      }
+    }
     // stash (:116-119) and the MSB logits: a lane's UP rows are consecutive — one store each when the whole tile lies inside the
     // split (wave-uniform test), else row by row against the descriptor's end
     if (t0 + TILE <= hi) {
@@ -399,7 +431,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
         }
         bstore<UP / 2>(rs_st, vo_st, t0 * 2, sw);
       }
-      if (PASS == 1) bstore<UP>(rs_lgw, vo_lw, t0 * 4, lw);
+      if (PASS == 1 || SO) bstore<UP>(rs_lgw, vo_lw, t0 * 4, lw);
     } else {
 #pragma unroll
       for (int u = 0; u < UP; ++u) {
@@ -410,7 +442,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
           const T sv = DT<T>::from_f32(s);
           __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const unsigned short*>(&sv), rs_st, vo_st, (t0 + u) * 2, 0);
         }
-        if (PASS == 1) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(s), rs_lgw, vo_lw, (t0 + u) * 4, 0);
+        if (PASS == 1 || SO) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(s), rs_lgw, vo_lw, (t0 + u) * 4, 0);
       }
     }
     float m_new = m_run;
@@ -435,6 +467,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       const float pj = __expf(sc[u] - m_run);      // exp(-inf) = 0; m_run is finite once a valid row has been seen
       const float pz = (sc[u] == -INFINITY) ? 0.f : pj;
       l_run += pz;
+      if (SO) continue;
       const float wgt = pz * __uint_as_float(tl.vs[u]);
       fma_piece<VB, VW>(o16, tl.vw[u], wgt);
       off_run += wgt;
@@ -527,11 +560,11 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
     }
   };
   if (p.S == 1) {
-    if (tid < D) outp[tid] = DT<T>::from_f32(o_tot / l_tot);
+    if (!SO && tid < D) outp[tid] = DT<T>::from_f32(o_tot / l_tot);
     if (p.lse != nullptr && tid == 0) { float* ls = p.lse + (int64_t)unit * 2; ls[0] = m_run; ls[1] = l_tot; }
     const bool need1 = PASS == 1 && (1.0f / l_tot) < p.thr;                              // max prob = exp(0) / sum
     if (PASS == 1 && tid == 0) p.need[unit] = need1 ? 1 : 0;
-    if (p.head_abs != nullptr) add_head_abs(o_tot / l_tot, tid < D, !need1);
+    if (!SO && p.head_abs != nullptr) add_head_abs(o_tot / l_tot, tid < D, !need1);
     return;
   }
 
@@ -543,7 +576,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
     if (tid == kPqvThreads - 1)
       s_ticket = __hip_atomic_fetch_add(p.ws_cnt + 2 * unit, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (tid < D && tid < kPqvThreads - kWave) pqv_store_granule(part + tid, o_tot, tag);
+  if (!SO && tid < D && tid < kPqvThreads - kWave) pqv_store_granule(part + tid, o_tot, tag);     // (SO: (max, sum) only)
   if (tid == D) { pqv_store_granule(part + D, m_run, tag); pqv_store_granule(part + D + 1, l_tot, tag); }
   if (p.poll_merge) {
     if (split != p.S - 1) return;
@@ -566,7 +599,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
         for (int k = 0; k < KBm; ++k) {
           const int sc_ = (s0 + k * Gr) < p.S ? (s0 + k * Gr) : g;
           const unsigned long long* qg = ws + (int64_t)sc_ * (D + 2);
-          ga[k] = __hip_atomic_load(qg + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ga[k] = SO ? ((unsigned long long)tag << 32) : __hip_atomic_load(qg + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           gm[k] = __hip_atomic_load(qg + D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           gl[k] = __hip_atomic_load(qg + D + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -623,8 +656,8 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       mg = mn;
     }
   }
-  if (g == 0) outp[e] = DT<T>::from_f32(og / lg);
-  if (p.head_abs != nullptr) {
+  if (!SO && g == 0) outp[e] = DT<T>::from_f32(og / lg);
+  if (!SO && p.head_abs != nullptr) {
     if (PASS == 1 && tid == 0) s_ticket = (1.0f / lg) < p.thr ? 1u : 0u;
     if (PASS == 1) __syncthreads();
     add_head_abs(og / lg, g == 0, !(PASS == 1 && s_ticket != 0u));
@@ -647,7 +680,7 @@ template <typename K> static int resident_capacity(K kernel) {
   return std::max(1, std::min(per_cu, 2)) * cus;
 }
 
-template <typename T, int D, int KB, int VB>
+template <typename T, int D, int KB, int VB, bool SO = false>
 static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, int env_poll, hipStream_t st) {
   const bool app = p.k_new != nullptr;
   constexpr int UP = SPATTEN_PQV_UP;
@@ -677,20 +710,24 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, in
     p2.poll_merge = (env_poll != 0 && S2 > 1) ? 1 : 0;
   }
   const dim3 grid2((unsigned)p2.S, (unsigned)n_active, (unsigned)p.B);
+  // (SO: the scores-only kernels need no more registers than the full ones — the capacities above stay a safe bound)
   if (dyn) {
-    if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, true>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP>), grid, blk, 0, st, p);
-    if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP>), grid2, blk, 0, st, p2);
+    if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, true, SO>), grid, blk, 0, st, p);
+    else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, SO>), grid, blk, 0, st, p);
+    if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, SO>), grid2, blk, 0, st, p2);
   } else {
-    if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, true>), grid, blk, 0, st, p);
-    else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP>), grid, blk, 0, st, p);
-    if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP>), grid2, blk, 0, st, p2);
+    if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, true, SO>), grid, blk, 0, st, p);
+    else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, SO>), grid, blk, 0, st, p);
+    if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, SO>), grid2, blk, 0, st, p2);
   }
   return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
 }
 
+// the local-V extras of spatten_attn_decode_pq_local_v (NULL: the plain profiled step)
+struct PqLvExtra { float* acc; int64_t acc_sh; const float* prev_lse; int prev_len; };
+
 template <typename T>
-static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st) {
+static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st, const PqLvExtra* lv = nullptr) {
   const int kb = a->planes->key_msb_bits;      // (the value width follows: supported profiles are (4, 8), (8, 8), (6, 6))
   const int d = a->head_dim;
   const int n_active = a->head_ids ? a->n_active_heads : a->heads;
@@ -731,8 +768,12 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
   p.k_new = (const T*)a->k_new; p.v_new = (const T*)a->v_new; p.new_sb = a->new_sb; p.new_sh = a->new_sh;
   p.kc = (T*)a->k_cache; p.krc = (T*)a->kr_cache; p.vc = (T*)a->v_cache; p.kv_sb = a->kv_sb; p.kv_sh = a->kv_sh;
   p.nr_row = a->step_state ? 1 : std::min(a->kv_len - 1, a->table_rows - 1);
+  p.acc = lv ? lv->acc : nullptr; p.acc_sh = lv ? lv->acc_sh : 0;
+  p.prev_lse = (lv && lv->acc) ? lv->prev_lse : a->lse; p.prev_len = (lv && lv->acc) ? lv->prev_len : 0;
   const bool dyn = a->step_state != nullptr, msb_only = (a->flags & SPATTEN_PQ_MSB_PASS_ONLY) != 0;
-#define SPATTEN_PQV(DD, KB, VB) return launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, env_poll, st)
+#define SPATTEN_PQV(DD, KB, VB)                                                                     \
+  return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, env_poll, st)            \
+            : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, env_poll, st)
   if (d == 128) {
     if (kb == 4) SPATTEN_PQV(128, 4, 8);
     if (kb == 8) SPATTEN_PQV(128, 8, 8);
@@ -744,13 +785,197 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
 #undef SPATTEN_PQV
 }
 
+// ================================================================================================
+// Local V pruning over the planes (spatten_attn_decode_pq_local_v): after the scores-only passes, the kept rows of every
+// launched head (top-keep of the stash row, ties lowest index first) and P.V over only those rows of the quantised V plane
+// with the full-row probabilities of the final fp32 logits (no renormalisation; SpAttenController.scala:546-558,591-612)
+// ================================================================================================
+constexpr int kLvMaxPer = 1024;         // kept rows per gather workgroup (their (row, weight) pairs live in LDS)
+constexpr int kLvMaxSplits = 64;
+static inline size_t lv_cnt_bytes(size_t units) { return (units * sizeof(unsigned) + 255) / 256 * 256; }
+
+// kept count of a unit: keep (host form) or ceil(keep_frac * length) in fp64 (device length: what math.ceil gives), in [1, n];
+// the device length is clamped to the launch's bound
+__device__ inline int pqlv_kept(const int32_t* step, int bound, int keep, double frac, int& n) {
+  n = step ? min(step[0], bound) : bound;
+  const int k = step ? (int)ceil(frac * (double)n) : keep;
+  return max(1, min(k, n));
+}
+
+template <typename T>
+__global__ __launch_bounds__(kSelThreads) void pqlv_select_kernel(const T* stash, int64_t sc_sb, int64_t sc_sh,
+                                                                  const int32_t* head_ids, const int32_t* step, int bound,
+                                                                  int keep, double frac, int32_t* idx, int64_t idx_sr, int H) {
+  const int h = head_ids ? head_ids[blockIdx.x] : (int)blockIdx.x, b = blockIdx.y;
+  int n;
+  const int k = pqlv_kept(step, bound, keep, frac, n);
+  topk_select_row<T>(stash + b * sc_sb + h * sc_sh, n, k, 0, idx + (int64_t)(b * H + h) * idx_sr);
+}
+
+template <typename T>
+struct PqlvGatherParams {
+  const int32_t* head_ids; const int32_t* step; const int32_t* idx; int64_t idx_sr;
+  PlanesDev pl;
+  const float* lse; float* prev_lse; float* head_abs;
+  T* out; int64_t out_sb;
+  float* part; unsigned* cnt;
+  int H, Hkv, bound, keep, per; double frac;
+};
+
+// grid (S, n_active, B): workgroup `split` takes kept entries [split * per, split * per + per) — (row, weight) pairs into LDS,
+// then the rows' V pieces (lane c of a row's D/16 lanes decodes its piece of 16 fields: the plane's piece layout), U rows in
+// flight per lane.  Partials go to the workspace; the LAST workgroup of a unit to arrive (ticket, no waiting) adds them in split
+// order, writes the output, the head importance, and copies the unit's (max, sum) to prev_lse for the next step's fold.
+template <typename T, int D, int VB>
+__global__ __launch_bounds__(256) void pqlv_gather_kernel(const PqlvGatherParams<T> p) {
+  constexpr int LPR = D / 16, RPI = 256 / LPR, U = 4, VW = VB / 2, VROW = D * VB / 8, HALF = D / 2;
+  constexpr float bias = (float)(1 << (VB - 1));
+  __shared__ int s_j[kLvMaxPer];
+  __shared__ float s_p[kLvMaxPer];
+  __shared__ float s_o[4][D];
+  __shared__ float s_abs[4];
+  __shared__ unsigned s_ticket;
+  const int split = blockIdx.x, S = gridDim.x, b = blockIdx.z, tid = threadIdx.x;
+  const int c = tid % LPR, r = tid / LPR, lane = tid & 63, wave = tid >> 6;
+  const int h = p.head_ids ? p.head_ids[blockIdx.y] : (int)blockIdx.y;
+  const int hkv = p.Hkv == p.H ? h : h / (p.H / p.Hkv);
+  const int unit = b * p.H + h;
+  int n;
+  const int k = pqlv_kept(p.step, p.bound, p.keep, p.frac, n);
+  const int32_t* ix = p.idx + (int64_t)unit * p.idx_sr;
+  const float* lgr = p.pl.lg + b * p.pl.lg_sb + h * p.pl.lg_sh;
+  const float* vsr = p.pl.vs + b * p.pl.sc_sb + hkv * p.pl.sc_sh;
+  const uint8_t* vqr = p.pl.vq + b * p.pl.vq_sb + hkv * p.pl.vq_sh;
+  const float m = p.lse[2 * unit], l = p.lse[2 * unit + 1];
+  const float mu = (m == -INFINITY) ? 0.f : m;
+  const int i_lo = split * p.per;
+  const int cnt_n = max(0, min(p.per, k - i_lo));
+  for (int t = tid; t < cnt_n; t += 256) {
+    const int j = ix[i_lo + t];
+    s_j[t] = j;
+    s_p[t] = __expf(lgr[j] - mu) / l * vsr[j];        // probability x the row's value scale
+  }
+  __syncthreads();
+  float o[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) o[e] = 0.f;
+  for (int i0 = 0; i0 < cnt_n; i0 += RPI * U) {
+    uint32_t w[U][VW];
+    float pp[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = i0 + u * RPI + r;
+      const bool ok = i < cnt_n;
+      const int j = s_j[ok ? i : 0];
+      pp[u] = ok ? s_p[i] : 0.f;
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(vqr + (int64_t)j * VROW + 2 * VB * c);
+#pragma unroll
+      for (int x = 0; x < VW; ++x) w[u][x] = src[x];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int t = 0; t < 16; ++t) o[t] = fmaf(pp[u], field_f32<VB, VW>(w[u], t) - bias, o[t]);
+  }
+  // reduce the rows of the wave (lanes with equal c), then the 4 waves
+#pragma unroll
+  for (int off = LPR; off < kWave; off <<= 1)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[e] += __shfl_xor(o[e], off, kWave);
+  if (lane < LPR)
+#pragma unroll
+    for (int t = 0; t < 8; ++t) { s_o[wave][8 * lane + t] = o[t]; s_o[wave][HALF + 8 * lane + t] = o[8 + t]; }
+  __syncthreads();
+  float tot = 0.f;
+  if (tid < D) tot = (s_o[0][tid] + s_o[1][tid]) + (s_o[2][tid] + s_o[3][tid]);
+  T* orow = p.out + b * p.out_sb + (int64_t)h * D;
+  if (S > 1) {
+    // partials leave as write-through (agent-scope) stores; the ticket is drawn after they were acknowledged (cascade.hip)
+    float* mine = p.part + ((int64_t)unit * kLvMaxSplits + split) * D;
+    if (tid < D) __hip_atomic_store(mine + tid, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) s_ticket = __hip_atomic_fetch_add(p.cnt + unit, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (s_ticket != (unsigned)(S - 1)) return;
+    if (tid < D) {
+      const float* q = p.part + (int64_t)unit * kLvMaxSplits * D + tid;
+      float acc = 0.f;
+      for (int s0 = 0; s0 < S; s0 += 8) {          // 8 loads in flight, added in split order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          v[u] = __hip_atomic_load(q + (int64_t)min(s0 + u, S - 1) * D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc += (s0 + u < S) ? v[u] : 0.f;
+      }
+      tot = acc;
+    }
+    if (tid == 0) __hip_atomic_store(p.cnt + unit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
+  }
+  if (tid < D) orow[tid] = DT<T>::from_f32(tot);
+  if (p.head_abs != nullptr) {     // head importance (README.md:21) of the value left in `out`, in a fixed order
+    const float v = wave_sum(tid < D ? fabsf(DT<T>::round(tot)) : 0.f);
+    if (lane == 0) s_abs[wave] = v;
+    __syncthreads();
+    if (tid == 0) p.head_abs[unit] += (s_abs[0] + s_abs[1]) + (s_abs[2] + s_abs[3]);
+  }
+  if (p.prev_lse != nullptr && tid < 2) p.prev_lse[2 * unit + tid] = p.lse[2 * unit + tid];
+}
+
+template <typename T, int D>
+static int launch_pqlv_gather(const PqlvGatherParams<T>& g, int vb, int S, int n_active, int B, hipStream_t st) {
+  const dim3 grid((unsigned)S, (unsigned)n_active, (unsigned)B);
+  if (vb == 8) hipLaunchKernelGGL((pqlv_gather_kernel<T, D, 8>), grid, dim3(256), 0, st, g);
+  else hipLaunchKernelGGL((pqlv_gather_kernel<T, D, 6>), grid, dim3(256), 0, st, g);
+  return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
+}
+
+template <typename T>
+static int run_pq_local_v(const spatten_pq_local_v_args_t* la, const PlanesDev& pd, hipStream_t st) {
+  const spatten_pq_decode_args_t* a = &la->step;
+  const int n_active = a->head_ids ? a->n_active_heads : a->heads;
+  const size_t units = (size_t)a->batch * a->heads;
+  const bool dyn = a->step_state != nullptr;
+  // the gather's slices are sized by a bound of the kept count: ceil(keep_fraction * the layout length) when a fraction is given
+  // (the device-length form, and a host-form launch that names its fraction: both then add the same slices in the same order —
+  // bit-identical outputs), else the host count itself
+  const int lay = (!dyn && a->kv_len_layout > a->kv_len) ? a->kv_len_layout : a->kv_len;
+  const int kf = la->keep_fraction > 0.0 ? (int)std::min<double>(std::ceil(la->keep_fraction * (double)lay), (double)lay) : 0;
+  const int k_bound = std::max({1, kf, dyn ? 0 : std::min(la->keep, a->kv_len)});
+  int per = ceil_div((int)(((long long)k_bound * n_active * a->batch + 1023) / 1024), 16) * 16;
+  per = std::max(per, 64);
+  per = std::min(per, kLvMaxPer);
+  per = std::max(per, ceil_div(k_bound, kLvMaxSplits));
+  if (per > kLvMaxPer) return SPATTEN_ERR_UNSUPPORTED;          // more than 65536 kept rows per head
+  const int S = ceil_div(k_bound, per);
+  unsigned* cnt = (unsigned*)la->workspace;
+  float* part = (float*)((char*)la->workspace + lv_cnt_bytes(units));
+  int32_t* idx = (int32_t*)((char*)part + units * kLvMaxSplits * (size_t)a->head_dim * sizeof(float));
+
+  PqLvExtra ex{la->importance_acc, la->acc_sh, la->prev_lse, la->prev_len};
+  int rc = run_pqv<T>(a, pd, st, &ex);                           // MSB pass + refetch pass, scores only
+  if (rc != SPATTEN_OK) return rc;
+  const int32_t* step = (const int32_t*)a->step_state;
+  hipLaunchKernelGGL((pqlv_select_kernel<T>), dim3((unsigned)n_active, (unsigned)a->batch), dim3(kSelThreads), 0, st,
+                     (const T*)a->scores, a->sc_sb, a->sc_sh, a->head_ids, step, a->kv_len, la->keep, la->keep_fraction, idx,
+                     (int64_t)la->workspace_rows, a->heads);
+  if (hipGetLastError() != hipSuccess) return SPATTEN_ERR_LAUNCH;
+  PqlvGatherParams<T> g;
+  g.head_ids = a->head_ids; g.step = step; g.idx = idx; g.idx_sr = la->workspace_rows;
+  g.pl = pd; g.lse = a->lse; g.prev_lse = la->prev_lse; g.head_abs = a->head_abs_acc;
+  g.out = (T*)a->out; g.out_sb = a->out_sb; g.part = part; g.cnt = cnt;
+  g.H = a->heads; g.Hkv = a->kv_heads; g.bound = a->kv_len; g.keep = la->keep; g.per = per; g.frac = la->keep_fraction;
+  if (a->head_dim == 128) return launch_pqlv_gather<T, 128>(g, a->planes->value_bits, S, n_active, a->batch, st);
+  return launch_pqlv_gather<T, 64>(g, a->planes->value_bits, S, n_active, a->batch, st);
+}
+
 }  // namespace spatten
 
 using namespace spatten;
 
-extern "C" int spatten_attn_decode_pq(const spatten_pq_decode_args_t* a, void* stream) {
+static int pq_validate(const spatten_pq_decode_args_t* a, PlanesDev& pd) {
   if (!a || a->struct_size != sizeof(spatten_pq_decode_args_t)) return SPATTEN_ERR_INVALID;
-  PlanesDev pd;
   if (!a->q || !a->out || !a->cos || !a->sin || !a->need_lsb || !planes_to_dev(a->planes, pd)) return SPATTEN_ERR_INVALID;
   if (a->batch <= 0 || a->heads <= 0 || a->kv_heads <= 0 || a->heads % a->kv_heads != 0 || a->kv_len <= 0) return SPATTEN_ERR_INVALID;
   if (!a->step_state && (a->pos_q < 0 || a->pos_q >= a->table_rows)) return SPATTEN_ERR_INVALID;
@@ -762,7 +987,35 @@ extern "C" int spatten_attn_decode_pq(const spatten_pq_decode_args_t* a, void* s
   if (!ok_dtype(a->dtype)) return SPATTEN_ERR_INVALID;
   if (a->head_dim != 64 && a->head_dim != 128) return SPATTEN_ERR_UNSUPPORTED;
   if (!pq_profile_supported(a->planes->key_msb_bits, a->planes->value_bits)) return SPATTEN_ERR_UNSUPPORTED;
+  return SPATTEN_OK;
+}
+
+extern "C" int spatten_attn_decode_pq(const spatten_pq_decode_args_t* a, void* stream) {
+  PlanesDev pd;
+  const int rc = pq_validate(a, pd);
+  if (rc != SPATTEN_OK) return rc;
   if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream);
   if (a->dtype == SPATTEN_F16) return run_pqv<f16_t>(a, pd, (hipStream_t)stream);
   return run_pqv<float>(a, pd, (hipStream_t)stream);
+}
+
+extern "C" size_t spatten_pq_local_v_workspace_bytes(int batch, int heads, int head_dim, int max_kv_len) {
+  if (batch <= 0 || heads <= 0 || head_dim <= 0 || max_kv_len <= 0) return 0;
+  const size_t units = (size_t)batch * heads;
+  return lv_cnt_bytes(units) + units * kLvMaxSplits * (size_t)head_dim * sizeof(float) + units * (size_t)max_kv_len * sizeof(int32_t);
+}
+
+extern "C" int spatten_attn_decode_pq_local_v(const spatten_pq_local_v_args_t* la, void* stream) {
+  if (!la || la->struct_size != sizeof(spatten_pq_local_v_args_t)) return SPATTEN_ERR_INVALID;
+  const spatten_pq_decode_args_t* a = &la->step;
+  PlanesDev pd;
+  const int rc = pq_validate(a, pd);
+  if (rc != SPATTEN_OK) return rc;
+  if (a->flags != 0 || !a->scores || !a->lse || !pd.lg || !la->workspace || la->workspace_rows < a->kv_len) return SPATTEN_ERR_INVALID;
+  if (a->step_state ? !(la->keep_fraction > 0.0 && la->keep_fraction <= 1.0) : (la->keep <= 0 || !(la->keep_fraction >= 0.0 && la->keep_fraction <= 1.0)))
+    return SPATTEN_ERR_INVALID;
+  if (la->importance_acc && (!la->prev_lse || la->prev_len < 0 || (!a->step_state && la->prev_len > a->kv_len))) return SPATTEN_ERR_INVALID;
+  if (a->dtype == SPATTEN_BF16) return run_pq_local_v<bf16_t>(la, pd, (hipStream_t)stream);
+  if (a->dtype == SPATTEN_F16) return run_pq_local_v<f16_t>(la, pd, (hipStream_t)stream);
+  return run_pq_local_v<float>(la, pd, (hipStream_t)stream);
 }

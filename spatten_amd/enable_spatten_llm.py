@@ -75,7 +75,10 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
     quantisation of the keys at decode: MSB plane first, LSB refetch below this max-probability), ``pq_profile`` ((key MSB
     bits, value bits) of the planes: (4, 8), (8, 8) or (6, 6) — the quantised VALUE plane and the LSB-only refetch;
     MatrixFetcher.scala:48-51, TestSpAtten.scala:64,83-97,173-176; None = 4-bit MSB plane, V in the model dtype), ``local_v_keep``
-    (local V pruning at decode: fraction of the keys whose V row is fetched), ``layer_keep`` (layer-to-layer cascade token
+    (local V pruning at decode: fraction of the keys whose V row is fetched; together with ``pq_profile`` the composed step over
+    the quantised planes — MSB scores, LSB refetch, V only for the kept keys from the quantised V plane — which also carries
+    ``importance_mode="cascade"`` and ``head_keep`` and is captured by ``auto_graph``; ``local_v_keep=1.0`` keeps every V row and is
+    how a profile combines with cascade importance), ``layer_keep`` (layer-to-layer cascade token
     pruning: one important-token count per layer, non-increasing — the surviving set shrinks through the layers),
     ``token_scope="global"`` (ONE kept token set per layer shared by all heads, ranked by the importance summed over the
     heads — README.md:21, workloads/small.csv:1; head-parallel ranks all-reduce the [layers, L] sums once per prune event;

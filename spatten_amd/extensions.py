@@ -23,6 +23,11 @@ against those restatements.
                                 With a profile the refetch pass reads ONLY the LSB plane (+ the stashed MSB logits).
     local_v_keep=f              local V pruning at decode (SpAttenController.scala:546-558,591-612): only the
                                 ceil(f * kv_len) most probable keys of a head fetch their V row.
+    pq_profile + local_v_keep   the whole cascade of the RTL in one decode step (spatten_attn_decode_pq_local_v): MSB scores,
+                                LSB refetch for the flagged heads, V fetched only for the kept keys and only from the quantised
+                                V plane, with or without importance_mode="cascade" (fused, deferred by one step as above) and
+                                head_keep.  local_v_keep=1.0 runs this path with every V row kept — the way to combine a
+                                profile with cascade importance.
     layer_keep=[k_0..k_L-1]     layer-to-layer cascade token pruning (README.md:11; the traces' key_fetch_num shrinks layer
                                 by layer): at a prune event layer l keeps k_l tokens of its window, chosen among the
                                 tokens layer l-1 just kept — the surviving set shrinks through the layers.  Caches of
@@ -57,6 +62,7 @@ class LayerState:
         self.pruned_ids: Optional[torch.Tensor] = None              # int64 pruned heads
         self.need_lsb: Optional[torch.Tensor] = None                # int32 [B*H]
         self.out: Optional[torch.Tensor] = None                     # [B, H*d], zero in the pruned heads' slices
+        self.pq_planes = None           # the profiled local-V step: the planes whose msb_logit holds the last step's logits
 
     def ensure(self, B, H, d, n, dtype, device, want_acc):
         cap = kv_slab.round_capacity(n + kv_slab.GROW)
@@ -105,12 +111,14 @@ class SpattenExtensions:
                 raise ValueError("pq_profile needs pq_threshold")
             if pq_profile not in ops.PQ_PROFILES:
                 raise ValueError(f"pq_profile {pq_profile}: one of {ops.PQ_PROFILES} (key MSB bits, value bits)")
-            if cascade:
+            if cascade and local_v_keep is None:
                 raise ValueError("pq_profile with importance_mode='cascade': the profiled decode launch does not carry the fused "
-                                 "accumulation — use the default planes (pq_profile=None)")
+                                 "accumulation — use the default planes (pq_profile=None), or local_v_keep (1.0 keeps every V "
+                                 "row) for the profiled local-V step, which does")
         self.pq_profile = pq_profile
-        if pq_threshold is not None and local_v_keep is not None:
-            raise ValueError("pq_threshold and local_v_keep cannot be combined (the local-V pass scores from the bf16 shadow)")
+        if pq_threshold is not None and local_v_keep is not None and pq_profile is None:
+            raise ValueError("pq_threshold and local_v_keep cannot be combined on the default planes (the local-V pass scores "
+                             "from the bf16 shadow) — set pq_profile for the local-V step over the quantised planes")
         if local_v_keep is not None and not (0.0 < float(local_v_keep) <= 1.0):
             raise ValueError("local_v_keep is a fraction in (0, 1]")
         self.cache = cache
@@ -142,8 +150,23 @@ class SpattenExtensions:
         one device-length launch, then the two passes over the planes); the layer cascade changes only the prune events (its
         layers decode on caches of different lengths: one step state per length).  Local V pruning is ONE launch whose kept
         count ceil(f * length) is evaluated on the device (round 4) — captured too, except together with cascade importance
-        (its accumulation there runs on host lengths)."""
-        return self.local_v_keep is None or not self.cascade
+        (its accumulation there runs on host lengths) — and the profiled local-V step (spatten_attn_decode_pq_local_v), whose
+        kept count and fused accumulation both follow the device length."""
+        return self.local_v_keep is None or not self.cascade or self.pq_local_v
+
+    @property
+    def pq_local_v(self) -> bool:
+        """The profiled planes with local V pruning: the composed step (spatten_attn_decode_pq_local_v)."""
+        return self.pq_profile is not None and self.local_v_keep is not None
+
+    def _pq_lv_planes(self, st, slab, upto: int, H: int):
+        """The slab's profiled planes, packed up to ``upto``; a pending step whose logits live in planes the slab has just
+        replaced is folded first (its fp32 logits go with the old planes)."""
+        slab.ensure_pq(upto, self.pq_profile, H)
+        if st.pq_planes is not None and st.pq_planes is not slab.pq:
+            self.flush(self.layers.index(st))
+        st.pq_planes = slab.pq
+        return slab.pq
 
     def decode_step_graph(self, layer: int, q, k_new, v_new, slab, kv_len: int, cos, sin, gctx):
         """The decode step under a DecodeGraph: every buffer at capacity and at a fixed address; with cascade importance
@@ -160,6 +183,24 @@ class SpattenExtensions:
             raise RuntimeError("extension buffers smaller than the slab capacity")
         casc = (st.acc, st.stash[1], st.lse[1], 0) if self.cascade else None
         step = gctx.state_for(slab, cos, sin)
+        if self.pq_local_v:
+            # the composed step: rows [0, kv_len - 1) packed with host lengths before the capture, the step's row appended and
+            # packed inside the MSB pass (all heads launched) or by spatten_kv_append_planes (a head list); the kept count, the
+            # fold's row count (state word 3) and the buffers are all device-side — one stash / lse pair, lse[1] = prev (max, sum)
+            planes = self._pq_lv_planes(st, slab, kv_len - 1, H)
+            if planes.capacity < cap:
+                raise RuntimeError("progressive-quant planes smaller than the slab capacity")
+            if st.head_ids is None:
+                app = (k_new, v_new, slab.k, slab.kr, slab.v)
+            else:
+                ops.kv_append_planes(k_new, v_new, slab.k, slab.kr, slab.v, planes, 0, cos, sin, step=step)
+                app = None
+            slab.pq_len = kv_len
+            ops.attn_decode_pq_local_v(q, planes, cap, cos, sin, 0, self.pq_threshold, 1, st.stash[0], st.lse[0], out=st.out,
+                                       need_lsb=st.need_lsb, keep_fraction=self.local_v_keep, head_ids=st.head_ids,
+                                       head_abs=st.head_abs if self.head_keep is not None else None,
+                                       cascade=(st.acc, st.lse[1], 0) if self.cascade else None, step=step, append=app)
+            return st.out, st.stash[0][:, :, None, :kv_len]
         if self.local_v_keep is not None:
             # local V pruning: the step's append in device-length form, then the one-launch step (the kept count follows the
             # device length); head pruning's zero-fill and head scores are stream operations on fixed buffers
@@ -219,7 +260,7 @@ class SpattenExtensions:
             if st.stash[0] is None:
                 continue
             if self.cascade:
-                st.parity = steps & 1
+                st.parity = 0 if self.pq_local_v else steps & 1
                 st.pending_len = n if steps > 0 else st.pending_len
 
     def decode_step(self, layer: int, q, k_new, v_new, slab, kv_len: int, past_len: int, cos, sin):
@@ -227,6 +268,8 @@ class SpattenExtensions:
         st = self.layers[layer]
         B, H, d = q.shape
         st.ensure(B, H, d, kv_len, q.dtype, q.device, self.cascade)
+        if self.pq_local_v:
+            return self._decode_step_pq_local_v(st, q, k_new, v_new, slab, kv_len, past_len, cos, sin)
         cur = st.parity
         st.parity ^= 1
         stash, lse = st.stash[cur], st.lse[cur]
@@ -272,6 +315,27 @@ class SpattenExtensions:
             st.pending_len = kv_len
         return st.out, stash[:, :, None, :kv_len]
 
+    def _decode_step_pq_local_v(self, st, q, k_new, v_new, slab, kv_len: int, past_len: int, cos, sin):
+        """The composed step with host lengths: one stash / lse pair (stash[0], lse[0]); lse[1] holds the previous step's
+        (max, sum), refreshed by the launch; the previous step's final logits stay in the planes' msb_logit until folded."""
+        B, H, d = q.shape
+        planes = self._pq_lv_planes(st, slab, past_len, H)
+        if st.head_ids is None:
+            app = (k_new, v_new, slab.k, slab.kr, slab.v)
+        else:
+            ops.kv_append_planes(k_new, v_new, slab.k, slab.kr, slab.v, planes, past_len, cos, sin)
+            app = None
+        slab.pq_len = kv_len
+        keep = max(1, min(kv_len, math.ceil(self.local_v_keep * kv_len)))
+        casc = (st.acc, st.lse[1], min(st.pending_len, kv_len)) if self.cascade else None
+        ops.attn_decode_pq_local_v(q, planes, kv_len, cos, sin, past_len, self.pq_threshold, keep, st.stash[0], st.lse[0],
+                                   out=st.out, keep_fraction=self.local_v_keep, need_lsb=st.need_lsb, head_ids=st.head_ids,
+                                   head_abs=st.head_abs if self.head_keep is not None else None, cascade=casc,
+                                   layout=slab.capacity, append=app)
+        if self.cascade:
+            st.pending_len = kv_len
+        return st.out, st.stash[0][:, :, None, :kv_len]
+
     def prefill_uses_pq(self, dtype, head_dim: int, q_len: int) -> bool:
         """The PQ-keyed flash kernel covers 16-bit dtypes at head_dim 64 / 128 and blocks of more than 8 rows (shorter
         blocks / fp32 run the exact rows leg on the un-quantised shadow)."""
@@ -315,6 +379,12 @@ class SpattenExtensions:
     def flush(self, layer: int):
         """Fold the last decode step's probabilities (still pending) into the accumulator."""
         st = self.layers[layer]
+        if self.cascade and st.pending_len > 0 and self.pq_local_v:
+            # the composed step: the final fp32 logits of the last step are in its planes' msb_logit, its (max, sum) in lse[0]
+            n = st.pending_len
+            ops.importance_accumulate(st.acc, st.pq_planes.msb_logit[:, :, None, :n], st.lse[0][:, :, None, :])
+            st.pending_len = 0
+            return
         if self.cascade and st.pending_len > 0:
             last = st.parity ^ 1
             n = st.pending_len

@@ -205,7 +205,9 @@ class DecodeGraph:
                 exts.graph_sync(self.steps_traced, [self.length + o for o in self.offsets])
                 synced.add(id(exts))
             st = exts.layers[layer]
-            cur = ((self.steps_traced - 1) & 1) if (exts.cascade and self.steps_traced > 0) else 0
+            # (cascade importance swaps two stash buffers every step; the composed step over the quantised planes keeps one)
+            swap = exts.cascade and not exts.pq_local_v
+            cur = ((self.steps_traced - 1) & 1) if (swap and self.steps_traced > 0) else 0
             object.__setattr__(module, "attn_scores", st.stash[cur][:, :, None, :self.length_of(slab)])
 
     @property

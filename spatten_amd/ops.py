@@ -6,6 +6,7 @@ PyTorch is plumbing here: it owns device memory and the stream; every op below p
 from __future__ import annotations
 
 import ctypes
+import math
 import threading
 from typing import List, Optional, Sequence, Tuple
 
@@ -1481,6 +1482,108 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
         a.k_cache, a.kr_cache, a.v_cache = _ptr(k_cache), kr_cache.data_ptr(), v_cache.data_ptr()
         a.kv_sb, a.kv_sh = kr_cache.stride(0), kr_cache.stride(1)
     _lib.check(_lib.load().spatten_attn_decode_pq(ctypes.byref(a), stream), "spatten_attn_decode_pq")
+    return out
+
+
+_pqlv_ws_cache = _LRU(8)
+
+
+def _pq_local_v_workspace(batch, heads, head_dim, rows, device) -> torch.Tensor:
+    key = (batch, heads, head_dim, device, _stream())
+    ws = _pqlv_ws_cache.get(key)
+    if ws is None or ws[1] < rows:
+        rows = max(rows, ws[1] if ws is not None else 0)
+        n = _lib.load().spatten_pq_local_v_workspace_bytes(batch, heads, head_dim, rows)
+        ws = _pqlv_ws_cache.put(key, (torch.zeros(n, dtype=torch.uint8, device=device), rows))
+    return ws
+
+
+def attn_decode_pq_local_v(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: torch.Tensor, sin: torch.Tensor,
+                           pos_q: int, threshold: float, keep: int, scores: torch.Tensor, lse: torch.Tensor,
+                           out: Optional[torch.Tensor] = None, need_lsb: Optional[torch.Tensor] = None,
+                           keep_fraction: float = 0.0, head_ids: Optional[torch.Tensor] = None,
+                           head_abs: Optional[torch.Tensor] = None, cascade=None, step: Optional["StepState"] = None,
+                           layout: int = 0, n_splits: int = 0, workspace: Optional[DecodeWorkspace] = None,
+                           append=None) -> torch.Tensor:
+    """The SpAtten cascade of one decode step over the profiled planes (spatten_attn_decode_pq_local_v): MSB scores, LSB refetch
+    for the flagged heads (both scores only), the exact per-head top-``keep`` of the stash, P.V over only the kept rows of the
+    quantised V plane with the full-row probabilities of the final fp32 logits.  Arguments as ``attn_decode_pqv``; ``scores``
+    [B,H,>=kv_len] and ``lse`` [B,H,2] are required.  With ``step`` the kept count is ceil(keep_fraction * device length); in the
+    host form a ``keep_fraction`` (the one ``keep`` came from) lays the gather out for the layout length, as the step form does.
+    ``cascade`` = (acc [H, >=kv_len] fp32, prev_lse [B,H,2] fp32, prev_len): the previous step's probabilities (its final logits
+    in ``planes.msb_logit``, its (max, sum) in ``prev_lse``, which this call refreshes) are folded into acc for rows < prev_len
+    (with ``step``: state word 3).  Returns out [B, H*d]; ``need_lsb`` int32 [B*H] is written."""
+    _dev(q, planes.msb, cos, sin, out, need_lsb, scores, lse, head_ids, head_abs)
+    B, H, d = q.shape
+    Hkv = planes.msb.shape[1]
+    if Hkv != H:
+        raise NotImplementedError("attn_decode_pq_local_v: grouped-query caches are not supported")
+    if d != planes.d or q.stride(2) != 1 or cos.shape[1] * 2 != d:
+        raise ValueError("q [B,H,d] with contiguous rows; planes and rotary tables of the same head_dim")
+    if kv_len > planes.capacity or (step is None and max(kv_len, pos_q + 1) > cos.shape[0]) or layout > planes.capacity:
+        raise ValueError("kv_len exceeds the planes' capacity or the rotary table")
+    if planes.msb_logit.shape[1] != H:
+        raise ValueError("planes were allocated for another number of query heads")
+    if d not in (64, 128):
+        raise NotImplementedError(f"attn_decode_pq_local_v: head_dim {d} (64 or 128)")
+    if (planes.key_bits, planes.value_bits) not in PQ_PROFILES:
+        raise NotImplementedError(f"attn_decode_pq_local_v: bit profile {(planes.key_bits, planes.value_bits)}")
+    if scores.stride(2) != 1 or scores.shape[2] < kv_len or lse.dtype != torch.float32 or lse.numel() != B * H * 2:
+        raise ValueError("scores [B,H,>=kv_len] with contiguous rows; lse [B,H,2] fp32")
+    if out is None:
+        out = torch.empty(B, H * d, dtype=q.dtype, device=q.device)
+    if need_lsb is None:
+        need_lsb = torch.empty(B * H, dtype=torch.int32, device=q.device)
+    stream = _stream()
+    ws = _pin(workspace) if workspace is not None else _workspace(B, H, d, q.device, stream)
+    lv_ws, lv_rows = _pq_local_v_workspace(B, H, d, max(int(kv_len), planes.capacity), q.device)
+    _pin(lv_ws)
+    la = _lib.PQLocalVArgs()
+    la.struct_size = ctypes.sizeof(_lib.PQLocalVArgs)
+    la.keep, la.keep_fraction = int(keep), float(keep_fraction)
+    la.workspace, la.workspace_rows = lv_ws.data_ptr(), int(lv_rows)
+    if cascade is not None:
+        acc, prev_lse, prev_len = cascade
+        _dev(acc, prev_lse)
+        if acc.dtype != torch.float32 or acc.stride(1) != 1 or acc.shape[0] != H or acc.shape[1] < kv_len \
+                or prev_lse.dtype != torch.float32 or prev_lse.numel() != B * H * 2:
+            raise ValueError("cascade: acc [H, >=kv_len] fp32 with contiguous rows, prev_lse [B,H,2] fp32")
+        la.importance_acc, la.acc_sh, la.prev_lse, la.prev_len = acc.data_ptr(), acc.stride(0), prev_lse.data_ptr(), int(prev_len)
+    a = la.step
+    a.struct_size = ctypes.sizeof(_lib.PQDecodeArgs)
+    a.dtype = _dt(q)
+    a.q, a.q_sb, a.q_sh = q.data_ptr(), (H * d if B == 1 else q.stride(0)), q.stride(1)
+    a.planes = ctypes.pointer(planes.desc)
+    a.cos, a.sin, a.table_rows, a.pos_q = cos.data_ptr(), sin.data_ptr(), cos.shape[0], int(pos_q)
+    a.out, a.out_sb = out.data_ptr(), out.stride(0)
+    a.scores, a.sc_sb, a.sc_sh = scores.data_ptr(), scores.stride(0), scores.stride(1)
+    a.lse = lse.data_ptr()
+    a.need_lsb, a.threshold, a.flags = need_lsb.data_ptr(), float(threshold), 0
+    a.workspace, a.workspace_splits = ws.buf.data_ptr(), ws.max_splits
+    a.batch, a.heads, a.kv_heads, a.head_dim, a.kv_len = B, H, Hkv, d, int(kv_len)
+    a.n_splits, a.kv_len_layout = int(n_splits), int(layout)
+    if head_ids is not None:
+        if head_ids.dtype != torch.int32 or head_ids.dim() != 1:
+            raise TypeError("head_ids must be a 1-D int32 device tensor")
+        a.head_ids, a.n_active_heads = head_ids.data_ptr(), head_ids.numel()
+    a.head_abs_acc = _ptr(head_abs)
+    a.step_state = None if step is None else step.data_ptr()
+    if append is not None:
+        k_new, v_new, k_cache, kr_cache, v_cache = append
+        _dev(k_new, v_new, k_cache, kr_cache, v_cache)
+        if k_new.shape != (B, Hkv, d) or k_new.stride(2) != 1 or v_new.stride() != k_new.stride():
+            raise ValueError("append: k_new / v_new [B,Hkv,d] with contiguous d and identical strides")
+        if kr_cache.stride(3) != 1 or kr_cache.stride(2) != d or v_cache.stride() != kr_cache.stride() \
+                or (k_cache is not None and k_cache.stride() != kr_cache.stride()) or kr_cache.shape[2] < kv_len:
+            raise ValueError("append: cache planes need contiguous rows (pitch d), identical strides and >= kv_len rows")
+        a.k_new, a.v_new, a.new_sb, a.new_sh = k_new.data_ptr(), v_new.data_ptr(), k_new.stride(0), k_new.stride(1)
+        a.k_cache, a.kr_cache, a.v_cache = _ptr(k_cache), kr_cache.data_ptr(), v_cache.data_ptr()
+        a.kv_sb, a.kv_sh = kr_cache.stride(0), kr_cache.stride(1)
+    rc = _lib.load().spatten_attn_decode_pq_local_v(ctypes.byref(la), stream)
+    if rc == -2:     # (head_dim and bit profile are checked above: what is left is the gather's bound)
+        kmax = max(int(keep), math.ceil(float(keep_fraction) * max(int(kv_len), int(layout))))
+        raise NotImplementedError(f"spatten_attn_decode_pq_local_v: {kmax} kept rows per head exceed the gather's 65536")
+    _lib.check(rc, "spatten_attn_decode_pq_local_v")
     return out
 
 
