@@ -145,9 +145,11 @@ template <int W> __device__ inline uint32_t piece_window(const uint32_t (&w)[W],
 __device__ inline float magic6_hi(uint32_t win) { return __uint_as_float(and_or_b32(win, 0x007E0000u, 0x42800000u)); }   // 64 + field at [17, 23)
 __device__ inline float magic6_lo(uint32_t win) { return __uint_as_float(and_or_b32(win, 0x0001F800u, 0x45800000u)); }   // 4096 + field at [11, 17)
 
-template <int BITS, int W> __device__ inline float dot_piece(const uint32_t (&w)[W], const float (&qv)[16]) {
+// MAGIC (keys): 16-bit outputs only, as fma_piece's — the 64 + f fields and the 96 qsum taken out cost an fp32 logit ~3 bits
+template <int BITS, int W, bool MAGIC = (BITS == 6 && SPATTEN_PQV_MAGIC6)>
+__device__ inline float dot_piece(const uint32_t (&w)[W], const float (&qv)[16]) {
   float a0 = 0.f, a1 = 0.f;
-  if constexpr (BITS == 6 && SPATTEN_PQV_MAGIC6) {       // every field at [17, 23): sum_t q_t (64 + f_t); the caller takes 64 qsum out
+  if constexpr (MAGIC) {       // every field at [17, 23): sum_t q_t (64 + f_t); the caller takes 64 qsum out
 #pragma unroll
     for (int t = 0; t < 16; t += 2) {
       a0 = fmaf(qv[t], magic6_hi(piece_window<W>(w, 6 * t - 17)), a0);
@@ -164,8 +166,12 @@ template <int BITS, int W> __device__ inline float dot_piece(const uint32_t (&w)
 }
 // (magic form: o[t] gains wgt * (4096 + f) for even t, wgt * (64 + f) for odd t: piece_bias6(t) * the weight sum is taken out at the end)
 __device__ inline float piece_bias6(int t) { return (t & 1) ? kMagic6Hi : kMagic6Lo; }
-template <int BITS, int W> __device__ inline void fma_piece(float (&o)[16], const uint32_t (&w)[W], float wgt) {
-  if constexpr (BITS == 6 && SPATTEN_PQV_MAGIC6) {
+// MAGIC: the magic form for 16-bit outputs only.  An fp32 output keeps the bits the 4096 would cost: through it the (6, 6) output
+// sat ~2^-17 of full scale off exact math, 12x the oracle's error (tests/test_gpu_pq_regimes.py); extract + convert keeps it at
+// the (8, 8) path's
+template <int BITS, int W, bool MAGIC = (BITS == 6 && SPATTEN_PQV_MAGIC6)>
+__device__ inline void fma_piece(float (&o)[16], const uint32_t (&w)[W], float wgt) {
+  if constexpr (MAGIC) {
 #pragma unroll
     for (int t = 0; t < 16; t += 2) {
       const uint32_t win = piece_window<W>(w, 6 * t - 11);     // field t at [11, 17), field t + 1 at [17, 23)
@@ -196,6 +202,8 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   constexpr int KROW = D * KBITS / 8;            // bytes of a key-plane row
   constexpr int VW = VB / 2;
   constexpr int VROW = D * VB / 8;
+  constexpr bool VMAGIC = VB == 6 && SPATTEN_PQV_MAGIC6 && sizeof(T) < 4;     // (fma_piece)
+  constexpr bool KMAGIC = KBITS == 6 && SPATTEN_PQV_MAGIC6 && sizeof(T) < 4;  // (dot_piece)
   using V8 = Vec8<T>;
 
   __shared__ float s_o[kPqvWaves][D + 2];
@@ -376,7 +384,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       // its MSB logit, exactly as a tile row's
       float a;
       if (KBITS == 4) a = NibbleDot<T>::dot(qn[0], pp.wm[0], 8.f) + NibbleDot<T>::dot(qn[1], pp.wm[KW - 1], 8.f);
-      else a = fmaf(-((float)(1 << (KB - 1)) + ((KBITS == 6 && SPATTEN_PQV_MAGIC6) ? kMagic6Hi : 0.f)), qsum, dot_piece<KBITS, KW>(pp.wm, qv));
+      else a = fmaf(-((float)(1 << (KB - 1)) + (KMAGIC ? kMagic6Hi : 0.f)), qsum, dot_piece<KBITS, KW, KMAGIC>(pp.wm, qv));
       a = group_sum<LPR>(a);
       const float sn = a * (pp.ks * (16.f * rsqrt_d));
       if (c == 0) {
@@ -386,7 +394,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       m_run = sn; l_run = 1.f;                           // the first key of this thread-row's softmax
       if (!SO) {
         const float wgt = pp.vs;
-        fma_piece<VB, VW>(o16, pp.wv, wgt);
+        fma_piece<VB, VW, VMAGIC>(o16, pp.wv, wgt);
         off_run = wgt;
       }
     }
@@ -401,7 +409,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
         a = NibbleDot<T>::dot(qn[0], tl.kw[u][0], PASS == 1 ? 8.f : 0.f) + NibbleDot<T>::dot(qn[1], tl.kw[u][KW - 1], PASS == 1 ? 8.f : 0.f);
       } else {               // fields hold msb + 2^(KB-1)
         // (an explicit fma: the appended row's logit is computed by the same expression elsewhere and must round the same way)
-        a = fmaf(-((float)(1 << (KB - 1)) + ((KBITS == 6 && SPATTEN_PQV_MAGIC6) ? kMagic6Hi : 0.f)), qsum, dot_piece<KBITS, KW>(tl.kw[u], qv));
+        a = fmaf(-((float)(1 << (KB - 1)) + (KMAGIC ? kMagic6Hi : 0.f)), qsum, dot_piece<KBITS, KW, KMAGIC>(tl.kw[u], qv));
       }
       a = group_sum<LPR>(a);
       const float s = a * (__uint_as_float(tl.ks[u]) * (PASS == 1 ? 16.f * rsqrt_d : rsqrt_d));
@@ -469,7 +477,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       l_run += pz;
       if (SO) continue;
       const float wgt = pz * __uint_as_float(tl.vs[u]);
-      fma_piece<VB, VW>(o16, tl.vw[u], wgt);
+      fma_piece<VB, VW, VMAGIC>(o16, tl.vw[u], wgt);
       off_run += wgt;
 #ifdef SPATTEN_PQV_PVBAR     // A/B: keep the row-groups' products apart (16 independent accumulators per row-group)
       __builtin_amdgcn_sched_barrier(0);
@@ -487,7 +495,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   {   // the fields hold qv + 2^(VB-1): take the constant out through the weight sum
     const float k = (float)(1 << (VB - 1)) * off_run;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) o16[i] -= (VB == 6 && SPATTEN_PQV_MAGIC6) ? fmaf(piece_bias6(i), off_run, k) : k;
+    for (int i = 0; i < 16; ++i) o16[i] -= VMAGIC ? fmaf(piece_bias6(i), off_run, k) : k;
   }
 
   // ---- reconcile the row groups (decode_attn.hip): per-wave max and sums in registers, one LDS hop across the waves ----
