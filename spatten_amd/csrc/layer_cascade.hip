@@ -328,7 +328,8 @@ __global__ __launch_bounds__(kChainThreads) void layer_cascade_select_kernel(con
 // stay in registers, every radix pass has its own histogram (cleared while the previous layer's rows are written), EVERY wave
 // scans the histogram itself (no broadcast round), and with a blocked layout the order-preserving compaction is one prefix over
 // threads (wave scan + the 16 wave totals): 4 barriers per layer.  Same keys, tie rule (lowest position first) and outputs as
-// chain_body, bit for bit (tests/test_gpu_cascade.py runs both).
+// chain_body, bit for bit (tests/test_gpu_layer_cascade.py runs both against the oracle, chain_body also at windows <= 4096 with
+// SPATTEN_LC_BLOCKED=0).
 constexpr int kBlk = 4;                       // window positions per thread
 constexpr int kBlkCopies = 4;                 // private histograms per pass
 template <typename T>
@@ -795,14 +796,16 @@ static int prune_layer_cascade_impl(int score_dtype, int kv_dtype, int layers, c
   if (env_blk < 0) { const char* e = getenv("SPATTEN_LC_BLOCKED"); env_blk = e ? atoi(e) : 1; }
   const bool blocked = env_blk != 0 && max_w <= kBlk * kChainThreads && c.map_ids > 0;
   if (blocked) {
-    static bool attr_blk[4] = {};
+    static bool attr_blk[64][4] = {};     // per DEVICE and score dtype, like attr_set above
     const int di = score_dtype == SPATTEN_F32 ? 0 : (score_dtype == SPATTEN_BF16 ? 1 : 2);
-    if (!attr_blk[di]) {
+    int dev_ = 0;
+    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 0;
+    if (!attr_blk[dev_][di]) {
       hipError_t e = hipSuccess;
       SPATTEN_BY_DTYPE(score_dtype, e = hipFuncSetAttribute((const void*)layer_cascade_select_blocked_kernel<T>,
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));   // = the map
       if (e != hipSuccess) return SPATTEN_ERR_LAUNCH;
-      attr_blk[di] = true;
+      attr_blk[dev_][di] = true;
     }
   }
   bool forked = false;
