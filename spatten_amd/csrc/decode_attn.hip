@@ -167,27 +167,20 @@ __device__ __forceinline__ void qkv_projection_waves(const DecodeParams<T>& p, f
       }
     }
   };
-#ifndef SPATTEN_FUSED_B1
-#define SPATTEN_FUSED_B1 0
-#endif
-  // B1 (a bare s_barrier: no vmcnt drain) tells the attention waves to issue their K/V tile.  Where: 0 = when the LAST weight
-  // pass has been issued (the tile queues behind two passes in flight), 1 = when only the last pass is still in flight,
-  // 2 = when every weight has landed (the memory pipe drains for one round trip, but the tile takes no bandwidth from the
-  // weights the query waits for)
+  // B1 (a bare s_barrier: no vmcnt drain) tells the attention waves to issue their K/V tile: when the LAST weight pass has
+  // been issued (the tile queues behind two passes in flight)
   SPATTEN_TSTAMP_T(8, kDecodeThreads);
   if (n_kb == 1) load_x(0);
   issue(pa, 0);
   for (int u = 0; u < n_units; u += 2) {         // n_units is even
     issue(pb, u + 1);
-    if (SPATTEN_FUSED_B1 == 0 && u + 2 >= n_units) __builtin_amdgcn_s_barrier();
+    if (u + 2 >= n_units) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     compute(pa, u);
     if (u + 2 < n_units) issue(pa, u + 2);
-    if (SPATTEN_FUSED_B1 == 1 && u + 2 >= n_units) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     compute(pb, u + 1);
   }
-  if (SPATTEN_FUSED_B1 == 2) __builtin_amdgcn_s_barrier();
   SPATTEN_TSTAMP_T(9, kDecodeThreads);           // every weight consumed, the split's elements published
   if (g == 0) {       // gather the head's q | k | v from its splits: 3 * D granules, 3 * D / 64 per lane, one round trip
     constexpr int PER = 3 * D / kWave;
@@ -301,10 +294,6 @@ __global__ __launch_bounds__(2 * kDecodeThreads) void decode_qkv_kernel(T* krc, 
     qkv_projection_waves<T, D, OPROJ>(p, s_x, s_y);
     return;
   }
-#if defined(SPATTEN_FUSED_EXP) && SPATTEN_FUSED_EXP == 1     // A/B harness only: what does the projection team alone take?
-  __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier();
-  return;
-#endif
   decode_body<T, D, UNR, 0, true, 0, true, false, false, DYN, true, OPROJ>(p, s_x);
 }
 
@@ -314,11 +303,11 @@ __global__ __launch_bounds__(2 * kDecodeThreads) void decode_qkv_kernel(T* krc, 
 // row-groups per tile.  Single-shot instantiation: 16-bit dtypes 10 (d = 128: 320 rows — a whole Llama-2-7B split — in
 // flight per workgroup).  Pipelined instantiation (chunks longer than that): two tiles of 4 (fp32: 2) row-groups.
 template <typename T, int D> constexpr int decode_unr() { return sizeof(T) == 4 ? (D == 256 ? 2 : 4) : (D == 256 ? 4 : 10); }
-#ifndef SPATTEN_DECODE_UP      // row-groups per pipelined tile, 16-bit dtypes.  r03 A/B at 16384 rows x 40 heads (tools/mb/dec_exp.sh
-                               // "-DSPATTEN_DECODE_UP=n"): 3: 55.7-56.5 us, 4: 55.3, 5: 56.2-56.7, 6: 58.1-58.7
-#define SPATTEN_DECODE_UP 4
-#endif
-template <typename T, int D> constexpr int decode_unr_pipe() { return sizeof(T) == 4 ? 2 : SPATTEN_DECODE_UP; }
+// row-groups per pipelined tile, 16-bit dtypes.  r03 A/B at 16384 rows x 40 heads: 3: 55.7-56.5 us, 4: 55.3, 5: 56.2-56.7,
+// 6: 58.1-58.7
+constexpr int kDecodeUp = 4;
+constexpr int kPqUp = 4;       // the same of the MSB-plane pass (see launch_decode)
+template <typename T, int D> constexpr int decode_unr_pipe() { return sizeof(T) == 4 ? 2 : kDecodeUp; }
 static inline int decode_group_rows(int d) { return kDecodeThreads / (d / 16); }
 
 // threads of the attention team of a single-row, single-shot decode step: 512 (two waves per SIMD, round 4) or 256
@@ -343,22 +332,19 @@ int decode_auto_splits(int units, int d, int kv_len, int elt, bool dense_rule) {
   // one workgroup per CU (the device's own count: ADVICE r05): measured best at Llama-2-7B decode sizes — more splits shorten
   // each workgroup's stream but lengthen the merge (a memory round trip per batch of partials)
   int s = coresident_workgroups() / (units > 0 ? units : 1);
-  static int env_s = -1;
-  if (env_s < 0) { const char* e = getenv("SPATTEN_DECODE_SPLITS"); env_s = e ? atoi(e) : 0; }
-  if (env_s > 0) s = env_s;
   const int max_by_len = ceil_div(kv_len, 2 * decode_group_rows(d));   // at least two row-groups per split
   if (s > max_by_len) s = max_by_len;
   // few units (a head-parallel rank holding 4-8 heads): the launch is pure latency, and every 16 further splits are one
   // more round trip of the merge — r03, 4 heads x 2081 rows: 33 splits 9.7 us, 16 splits 8.45; 5 heads x 8192 rows: 51
   // splits 12.4 us, 32 splits 10.9 (tools/probe_few_heads.py).  One round unless the rows are long enough to pay for more.
   const int cap_by_merge = std::max(16, ceil_div(kv_len, 256));
-  if (env_s <= 0 && s > cap_by_merge) s = cap_by_merge;
+  if (s > cap_by_merge) s = cap_by_merge;
   // r05 (tools/mb/split_sweep.py, 2081 rows): whenever EIGHT splits still hold their chunk in one single-shot tile, eight beat every
   // larger count — the merge folds up to 8 partials in one thread group (no LDS fold, no barrier) and a fuller tile costs nothing
   // while every load is issued up front: 4 / 8 / 16 / 24 / 28 heads 9.30 / 9.56 / 10.09 / 11.29 / 12.11 -> 8.84 / 9.04 / 9.58 /
   // 10.09 / 10.58 us (32 heads were at 8 already).  Longer rows (pipelined tiles) keep one workgroup per CU.
   // (dense_rule: measured on the 16-bit dense step only — the quantised-plane passes have other tile sizes and keep their count)
-  if (env_s <= 0 && dense_rule && elt == 2 && d != 256 && s > 8 && ceil_div(kv_len, 8) <= 10 * decode_group_rows(d)) s = 8;
+  if (dense_rule && elt == 2 && d != 256 && s > 8 && ceil_div(kv_len, 8) <= 10 * decode_group_rows(d)) s = 8;
   if (s < 1) s = 1;
   if (s > kDecodeMaxSplits) s = kDecodeMaxSplits;
   return s;
@@ -402,8 +388,8 @@ static int launch_decode(const DecodeParams<T>& p, int n_active, bool scores_onl
         }
       } else if (pipe) {
         // (r03, measured and NOT adopted: 6 / 8 row-groups per pipelined tile for this pass — a plane row is a quarter of
-        //  a 16-bit key row, so the registers are there — 22.9 / 23.3 us against 20.7 with 4; SPATTEN_PQ_UP keeps the A/B)
-        constexpr int UPQ = (sizeof(T) == 2 && D <= 128) ? SPATTEN_PQ_UP : UP;
+        //  a 16-bit key row, so the registers are there — 22.9 / 23.3 us against 20.7 with 4)
+        constexpr int UPQ = (sizeof(T) == 2 && D <= 128) ? kPqUp : UP;
         if (casc) SPATTEN_LAUNCH(UP, 0, false, 1, true, true, true); else SPATTEN_LAUNCH(UPQ, 0, false, 1, true, false, true);
         SPATTEN_LAUNCH(UP, 0, false, 2, true, false, true);
       } else {
@@ -438,27 +424,6 @@ static int launch_decode(const DecodeParams<T>& p, int n_active, bool scores_onl
     // length) — a step must not change its bits with its route; pipelined (long) chunks, the quantised-key passes and the
     // fused projection launch keep the 256-thread body.  spatten_decode_set_team(256) restores the r03 form process-wide.
     if constexpr (sizeof(T) == 2 && D == 128) {
-      static int env_pipe512 = -1;      // (A/B) the pipelined form of long chunks on the 512-thread team as well
-      if (env_pipe512 < 0) { const char* e = getenv("SPATTEN_DECODE_TEAM_PIPE"); env_pipe512 = e ? atoi(e) : 0; }
-      if (decode_team() == 512 && pipe && env_pipe512 && p.n_q == 1) {
-        constexpr int UP2 = (UP + 1) / 2;
-        const dim3 blk512(2 * kDecodeThreads);
-#define SPATTEN_LEAN512P(CC, DD)                                                                                                    \
-  hipLaunchKernelGGL((decode_lean_kernel<T, D, UP2, CC, true, DD, 2 * kDecodeThreads>), grid, blk512, 0, stream, p.krc, p.vc, p.q, p.cos, \
-                     p.sin, (int)p.kv_sb, (int)p.kv_sh, p.N, p.chunk, p.H, p.pos_q, p)
-#define SPATTEN_GEN512P(CC, DD) \
-  hipLaunchKernelGGL((decode_attn_kernel<T, D, UP2, 0, false, 0, true, CC, true, DD, 2 * kDecodeThreads>), grid, blk512, 0, stream, p)
-        if (lean && small) {
-          if (dyn) { if (casc) SPATTEN_LEAN512P(true, true); else SPATTEN_LEAN512P(false, true); }
-          else { if (casc) SPATTEN_LEAN512P(true, false); else SPATTEN_LEAN512P(false, false); }
-        } else {
-          if (dyn) { if (casc) SPATTEN_GEN512P(true, true); else SPATTEN_GEN512P(false, true); }
-          else { if (casc) SPATTEN_GEN512P(true, false); else SPATTEN_GEN512P(false, false); }
-        }
-#undef SPATTEN_LEAN512P
-#undef SPATTEN_GEN512P
-        return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
-      }
       if (decode_team() == 512 && !pipe && p.n_q == 1) {
         constexpr int U2 = (U + 1) / 2;
         const dim3 blk512(2 * kDecodeThreads);
@@ -566,10 +531,8 @@ int decode_rows(const DecodeCall& c, hipStream_t stream) {
   const size_t cnt_bytes = decode_cnt_bytes(c.ws_units);
   // single-hop merge (see the kernel): only when the grid cannot outnumber the workgroup slots of the chip.  Causal
   // multi-row launches are excluded (their later splits may be empty and return early... they still publish, but keep
-  // the conservative protocol there); SPATTEN_DECODE_POLL=0 forces the ticket protocol (A/B measurements).
-  static int env_poll = -1;
-  if (env_poll < 0) { const char* e = getenv("SPATTEN_DECODE_POLL"); env_poll = e ? atoi(e) : 1; }
-  const int poll_merge = (env_poll != 0 && S > 1 && c.n_q == 1 && (long long)S * n_active * c.batch <= coresident_workgroups()) ? 1 : 0;
+  // the conservative protocol there).
+  const int poll_merge = (S > 1 && c.n_q == 1 && (long long)S * n_active * c.batch <= coresident_workgroups()) ? 1 : 0;
 
   // ---- the output projection of the step (modify_llama.py:163) as a second launch of the same call: one C call per
   // layer-step for the host.  (r03: fusing it INTO the launch — projection waves in the decode workgroups that stream the
@@ -680,9 +643,7 @@ extern "C" int spatten_decode_qkv_supported(int dtype, int batch, int heads, int
   if (S > kv_len_layout) S = kv_len_layout;
   const int chunk = ceil_div(ceil_div(kv_len_layout, S), 8) * 8;
   S = ceil_div(kv_len_layout, chunk);
-  static int env_poll = -1;
-  if (env_poll < 0) { const char* e = getenv("SPATTEN_DECODE_POLL"); env_poll = e ? atoi(e) : 1; }
-  const int poll = (env_poll != 0 && S > 1 && (long long)S * heads * batch <= coresident_workgroups()) ? 1 : 0;
+  const int poll = (S > 1 && (long long)S * heads * batch <= coresident_workgroups()) ? 1 : 0;
   if (!decode_qkv_shape_ok(head_dim, S, poll)) return 0;
   return chunk <= 10 * decode_group_rows(head_dim) ? 1 : 0;      // a single-shot tile per split
 }

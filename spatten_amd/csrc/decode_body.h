@@ -99,9 +99,6 @@ struct DecodeParams {
                         // word 2 = a counter of that layer's completed units; the unit that completes the layer advances the epoch
 };
 
-#ifndef SPATTEN_PQ_UP
-#define SPATTEN_PQ_UP 4          // row-groups per pipelined tile of the MSB-plane pass (A/B switch, see launch_decode)
-#endif
 constexpr int kDecodeThreads = 256;
 constexpr int kGemvChunksFused = 8;      // = gemv.hip's kGemvChunks: the fused projection keeps its summation order
 // (co-residency bound of the polling merge: common.h coresident_workgroups() — the device's CU count, asked per device)
@@ -374,11 +371,9 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
     n_raw[1] = V8::ldg(p.sin + (int64_t)p.nr_row * HALF + 8 * c);
     gen_f = p.ws_cnt[(p.S > 1 ? 2 * unit + 1 : 0) + opaque_lane(0)];
     if (OPROJ) gen_y = p.ych_gen[opaque_lane(0)];
-#if !(defined(SPATTEN_FUSED_EXP) && SPATTEN_FUSED_EXP == 2)
     // B1 — a bare s_barrier: __syncthreads() carries a fence, i.e. `s_waitcnt vmcnt(0)`, and the projection waves would
     // drain their in-flight weight passes in front of it (r04: the fused launch then took 29.5 us, the two launches 29.0)
     __builtin_amdgcn_s_barrier();
-#endif
   }
   if (!CHAIN) issue_keys(tile_a, lo);
   if (!FUSED && !CHAIN) {   // the new token's un-rotated key and the rotary row of its slot N-1 (modify_llama.py:103-104)
@@ -402,9 +397,6 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
   // rotation (and the wait for the query) in front of the tile loads, which then leave one memory latency late
   __builtin_amdgcn_sched_barrier(0);
   if (FUSED) {
-#if defined(SPATTEN_FUSED_EXP) && SPATTEN_FUSED_EXP == 2      // A/B harness only: the tile goes out at kernel start
-    __builtin_amdgcn_s_barrier();
-#endif
     // B2: s_x holds the head's q | k | v (the writing wave drained its LDS stores in front of its s_barrier).  Bare again: the
     // tile loads of this wave stay in flight across it and are waited for one row-group at a time below
     __builtin_amdgcn_s_barrier();
@@ -665,15 +657,6 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
     if (owns_new && hi <= lo) process_tile(tile_a, lo, 0, true);
   }
 
-#ifdef SPATTEN_EXP_NOREDUCE   // A/B harness only: what does everything after the streaming loop cost?
-  {   // (every accumulator stays live: with only olo[0] written the compiler drops the upper-half value loads)
-    float keep = l_run + m_run;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) keep += olo[i] + ohi[i];
-    if (tid < D) p.out[b * p.out_sb + h * D + tid] = DT<T>::from_f32(keep);
-  }
-  return;
-#endif
   SPATTEN_TSTAMP(1);
   SPATTEN_CSTAMP(4);
   // ---- reconcile the row groups: per-wave max and sums (registers only), then ONE LDS hop across the waves ------
@@ -744,10 +727,6 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
       m_run = m_wg;
     }
   }
-#ifdef SPATTEN_EXP_NOMERGE    // A/B harness only: what do publish + ticket + merge cost?
-  if (tid < D) p.out[b * p.out_sb + h * D + tid] = DT<T>::from_f32(o_tot / l_tot);
-  return;
-#endif
   SPATTEN_TSTAMP(2);
   SPATTEN_CSTAMP(5);
   T* outp = p.out + b * p.out_sb + (LEAN ? 0 : qi * p.out_sq) + h * D;

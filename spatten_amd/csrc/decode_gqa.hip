@@ -39,13 +39,6 @@ static __device__ unsigned long long* g_gqa_trace = nullptr;
 // per tile k < 4 of a wave: 0 keys ready, 1 S done, 2 key refill issued, 3 softmax done, 4 values ready, 5 P.V done, 6 value refill issued
 #define SPATTEN_GSTAMP_IT(k, j) do { if ((k) < 4) SPATTEN_GSTAMP(12 + 8 * (k) + (j)); } while (0)
 
-#ifndef SPATTEN_GQA_NT             // A/B: non-temporal LDS-DMA requests
-#define SPATTEN_GQA_NT 1
-#endif
-#ifndef SPATTEN_GQA_SPLIT_REFILL   // A/B: a consumed stage is refilled in two halves (keys behind S, values behind P·V)
-#define SPATTEN_GQA_SPLIT_REFILL 1
-#endif
-
 namespace spatten {
 
 template <typename T>
@@ -113,13 +106,9 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   const i32x4 k_rsrc = rsrc_of(krb), v_rsrc = rsrc_of(vb);
   const unsigned lds_wbuf = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds + (unsigned)wave * WBUF;
   auto dma16a = [&](const i32x4& rsrc, unsigned lds_dst, int voff, int soff) {
-#if SPATTEN_GQA_NT      // non-temporal: every K / V byte is used once per launch
+    // non-temporal: every K / V byte is used once per launch
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen nt lds"
                  :: "s"(lds_dst), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-#else
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds_dst), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-#endif
   };
   auto dma_keys = [&](int tile, int stage) {
     const int ln = opaque_lane(lane);
@@ -281,14 +270,12 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
       }
     }
     SPATTEN_GSTAMP_IT(k, 1);
-#if SPATTEN_GQA_SPLIT_REFILL
     // the stage's KEY half is consumed (the reads that fed the products above have returned): the keys of the tile after next go
     // out now, a softmax and a P·V earlier than the stage's value half — a wave's requests then enter the CU's memory queue in two
     // bursts of 8 KiB per tile instead of one of 16
     __builtin_amdgcn_sched_barrier(0);
     if (more2) dma_keys(i + 2 * NW, stage);
     __builtin_amdgcn_sched_barrier(0);
-#endif
     SPATTEN_GSTAMP_IT(k, 2);
     // both reference roundings of every logit (matmul -> dtype, "/ sqrt(d)" -> dtype, modify_llama.py:111-113)
 #pragma unroll
@@ -380,11 +367,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     SPATTEN_GSTAMP_IT(k, 3);
     // ---- O^T += Vt · P^T: the tile's value rows have landed ------------------------------------------------------------------------
     __builtin_amdgcn_sched_barrier(0);
-#if SPATTEN_GQA_SPLIT_REFILL
     if (!edge) { if (more2) wait_vm<3 * NK>(); else if (more) wait_vm<2 * NK>(); else wait_vm<0>(); }   // (behind V: K, V of the next tile, K of the one after)
-#else
-    if (!edge) { if (more) wait_vm<2 * NK>(); else wait_vm<0>(); }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     SPATTEN_GSTAMP_IT(k, 4);
     {
@@ -408,11 +391,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     __builtin_amdgcn_sched_barrier(0);
     if (k == 0) SPATTEN_GSTAMP(4);   // first tile consumed
     SPATTEN_GSTAMP_IT(k, 5);
-#if SPATTEN_GQA_SPLIT_REFILL
     if (more2) dma_values(i + 2 * NW, stage);
-#else
-    if (more2) dma_tile(i + 2 * NW, stage);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     if (k == 0) SPATTEN_GSTAMP(6);   // its refill requested
     SPATTEN_GSTAMP_IT(k, 6);
@@ -588,9 +567,7 @@ static inline bool gqa_pays(int batch, int heads, int kv_heads, int rows, int ch
 // rows x 32 / 8 heads 12.6 -> 10.45 us, 4096 rows 13.2 -> 11.6 against two tiles per wave; 64 rows: as 128); chunks are whole tiles.
 static inline void gqa_layout(int cols, int lay, int n_splits, int ws_splits, int& S, int& chunk32) {
   S = n_splits > 0 ? n_splits : std::max(1, coresident_workgroups() / cols);
-  static int min_chunk = -1;                  // (SPATTEN_GQA_MIN_CHUNK: A/B of the shortest chunk a split may get)
-  if (min_chunk < 0) { const char* e = getenv("SPATTEN_GQA_MIN_CHUNK"); min_chunk = e ? std::max(32, atoi(e)) : 128; }
-  S = std::min(S, std::max(1, lay / min_chunk));
+  S = std::min(S, std::max(1, lay / 128));
   S = std::min(S, std::min(ws_splits, kDecodeMaxSplits));
   const int chunk = (lay + S - 1) / S;
   chunk32 = (chunk + 31) / 32 * 32;
@@ -620,9 +597,7 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   gqa_layout(cols, lay, c.n_splits, ws_splits, S, chunk32);
   if (mode < 0 && !gqa_pays(c.batch, c.heads, c.kv_heads, lay, chunk32)) return SPATTEN_ERR_UNSUPPORTED;
   if (S > 1 && (!c.workspace || (size_t)units > c.ws_units)) return SPATTEN_ERR_UNSUPPORTED;
-  static int env_poll = -1;
-  if (env_poll < 0) { const char* e = getenv("SPATTEN_DECODE_POLL"); env_poll = e ? atoi(e) : 1; }
-  const int poll_merge = (env_poll != 0 && S > 1 && (long long)S * cols <= coresident_workgroups()) ? 1 : 0;
+  const int poll_merge = (S > 1 && (long long)S * cols <= coresident_workgroups()) ? 1 : 0;
   const size_t cnt_bytes = decode_cnt_bytes(c.ws_units);
 
 #define SPATTEN_GQA_FILL(T)                                                                                      \

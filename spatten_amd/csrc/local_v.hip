@@ -97,17 +97,12 @@ __device__ unsigned long long* g_lv_trace = nullptr;
 #else
 #define LV_STAMP(slot)
 #endif
-#ifndef SPATTEN_LV_UK
-#define SPATTEN_LV_UK 6          // key row-groups per pipelined tile of phase 1
-#endif
-#ifndef SPATTEN_LV_UV
-#define SPATTEN_LV_UV 6          // value row-groups per pipelined tile of phase 3
-#endif
 
 template <typename T, int D, bool DYN>
 __global__ __launch_bounds__(kLvThreads) void local_v_kernel(const LvParams<T> p) {
   constexpr int LPR = D / 16, RPI = kLvThreads / LPR, HALF = D / 2;
-  constexpr int UK = SPATTEN_LV_UK, UV = SPATTEN_LV_UV;
+  constexpr int UK = 6;            // key row-groups per pipelined tile of phase 1
+  constexpr int UV = 6;            // value row-groups per pipelined tile of phase 3
   constexpr int NP = OKey<T>::kPasses;
   using V8 = Vec8<T>;
   using raw_t = typename V8::raw;

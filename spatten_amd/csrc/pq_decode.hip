@@ -61,18 +61,14 @@ struct PqvParams {
   float* acc; int64_t acc_sh; const float* prev_lse; int prev_len;
 };
 
-#ifndef SPATTEN_PQV_UP
-#define SPATTEN_PQV_UP 4          // row-groups per pipelined tile.  r04 A/B at 8192 rows x 32 heads, profile (4, 8), MSB pass:
-                                  // 12: 20.0 us, 8: 16.6, 6: 16.4, 4: 14.8 (tools/mb/pqv_ab.sh; rebuild with -DSPATTEN_PQV_UP=n)
-#endif
-#ifndef SPATTEN_PQV_THREADS     // A/B: 512 = two waves per SIMD (decode_attn.hip's 512-thread team).  r04 at 8192 rows x 32 heads, MSB pass of
-                                // the (4,8) / (8,8) / (6,6) profiles: 256 threads 14.9 / 17.3 / 16.0 us; 512 with UP = 4: 16.9 / 18.2 / 18.3; 512 with
-                                // UP = 2: 15.3 / 16.8 / 16.8 — the pipelined stream does not gain from the second wave.  256 stays.
-#define SPATTEN_PQV_THREADS 256
-#endif
+// row-groups per pipelined tile.  r04 A/B at 8192 rows x 32 heads, profile (4, 8), MSB pass: 12: 20.0 us, 8: 16.6, 6: 16.4, 4: 14.8
+constexpr int kPqvUp = 4;
+// (r04, 8192 rows x 32 heads, MSB pass of the (4,8) / (8,8) / (6,6) profiles: 256 threads 14.9 / 17.3 / 16.0 us; 512 (two waves per
+//  SIMD, decode_attn.hip's 512-thread team) with 4 row-groups 16.9 / 18.2 / 18.3, with 2: 15.3 / 16.8 / 16.8 — the pipelined stream does
+//  not gain from the second wave)
 // (r05, measured and dropped: THREE tiles in flight instead of two — (4,8) 14.5 -> 15.3-15.5 us, (8,8) 16.9 -> 18.0-18.2, with tiles of
 //  64 rows 14.7 / 17.7-18.1: the pass is not waiting for bytes in flight)
-constexpr int kPqvThreads = SPATTEN_PQV_THREADS;
+constexpr int kPqvThreads = 256;
 constexpr int kPqvWaves = kPqvThreads / 64;
 
 __device__ inline void pqv_store_granule(unsigned long long* g, float v, unsigned tag) {
@@ -124,9 +120,6 @@ template <int BITS, int W> __device__ inline float field_f32(const uint32_t (&w)
   else f = __builtin_amdgcn_alignbit(w[wi + 1 < W ? wi + 1 : wi], w[wi], off) & mask;
   return (float)f;
 }
-#ifndef SPATTEN_PQV_MAGIC6      // A/B: 6-bit fields through the mantissa (below) instead of extract + convert.  1 = on
-#define SPATTEN_PQV_MAGIC6 1
-#endif
 // 6-bit fields without a conversion (round 5): the 32-bit window that starts at bit `s` of the piece (one shift / v_alignbit) puts
 // a field into mantissa bits [P, P + 6) of an fp32 whose exponent makes the mantissa's bit P worth 1 — `(win & mask) | magic`
 // (one v_and_or_b32) IS the float 2^(23-P) + field, exactly; the constant leaves through the weight sum like the offset-binary
@@ -146,7 +139,7 @@ __device__ inline float magic6_hi(uint32_t win) { return __uint_as_float(and_or_
 __device__ inline float magic6_lo(uint32_t win) { return __uint_as_float(and_or_b32(win, 0x0001F800u, 0x45800000u)); }   // 4096 + field at [11, 17)
 
 // MAGIC (keys): 16-bit outputs only, as fma_piece's — the 64 + f fields and the 96 qsum taken out cost an fp32 logit ~3 bits
-template <int BITS, int W, bool MAGIC = (BITS == 6 && SPATTEN_PQV_MAGIC6)>
+template <int BITS, int W, bool MAGIC = (BITS == 6)>
 __device__ inline float dot_piece(const uint32_t (&w)[W], const float (&qv)[16]) {
   float a0 = 0.f, a1 = 0.f;
   if constexpr (MAGIC) {       // every field at [17, 23): sum_t q_t (64 + f_t); the caller takes 64 qsum out
@@ -169,7 +162,7 @@ __device__ inline float piece_bias6(int t) { return (t & 1) ? kMagic6Hi : kMagic
 // MAGIC: the magic form for 16-bit outputs only.  An fp32 output keeps the bits the 4096 would cost: through it the (6, 6) output
 // sat ~2^-17 of full scale off exact math, 12x the oracle's error (tests/test_gpu_pq_regimes.py); extract + convert keeps it at
 // the (8, 8) path's
-template <int BITS, int W, bool MAGIC = (BITS == 6 && SPATTEN_PQV_MAGIC6)>
+template <int BITS, int W, bool MAGIC = (BITS == 6)>
 __device__ inline void fma_piece(float (&o)[16], const uint32_t (&w)[W], float wgt) {
   if constexpr (MAGIC) {
 #pragma unroll
@@ -202,8 +195,8 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   constexpr int KROW = D * KBITS / 8;            // bytes of a key-plane row
   constexpr int VW = VB / 2;
   constexpr int VROW = D * VB / 8;
-  constexpr bool VMAGIC = VB == 6 && SPATTEN_PQV_MAGIC6 && sizeof(T) < 4;     // (fma_piece)
-  constexpr bool KMAGIC = KBITS == 6 && SPATTEN_PQV_MAGIC6 && sizeof(T) < 4;  // (dot_piece)
+  constexpr bool VMAGIC = VB == 6 && sizeof(T) < 4;     // (fma_piece)
+  constexpr bool KMAGIC = KBITS == 6 && sizeof(T) < 4;  // (dot_piece)
   using V8 = Vec8<T>;
 
   __shared__ float s_o[kPqvWaves][D + 2];
@@ -479,9 +472,6 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
       const float wgt = pz * __uint_as_float(tl.vs[u]);
       fma_piece<VB, VW, VMAGIC>(o16, tl.vw[u], wgt);
       off_run += wgt;
-#ifdef SPATTEN_PQV_PVBAR     // A/B: keep the row-groups' products apart (16 independent accumulators per row-group)
-      __builtin_amdgcn_sched_barrier(0);
-#endif
     }
   };
   for (int t0 = lo; t0 < hi; t0 += 2 * TILE) {
@@ -531,27 +521,14 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   __syncthreads();
   float o_tot = 0.f, l_tot = 0.f;
   {
-    if constexpr (kPqvWaves == 4) {
-      const float m0 = s_o[0][D + 1], m1 = s_o[1][D + 1], m2 = s_o[2][D + 1], m3 = s_o[3][D + 1];
-      const float m_wg = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-      const float mu = (m_wg == -INFINITY) ? 0.f : m_wg;
-      const float w0 = __expf(m0 - mu), w1 = __expf(m1 - mu), w2 = __expf(m2 - mu), w3 = __expf(m3 - mu);
-      if (tid < D) o_tot = (s_o[0][tid] * w0 + s_o[1][tid] * w1) + (s_o[2][tid] * w2 + s_o[3][tid] * w3);
-      l_tot = (s_o[0][D] * w0 + s_o[1][D] * w1) + (s_o[2][D] * w2 + s_o[3][D] * w3);
-      m_run = m_wg;
-    } else {
-      float mw[kPqvWaves], m_wg = -INFINITY;
-#pragma unroll
-      for (int w = 0; w < kPqvWaves; ++w) { mw[w] = s_o[w][D + 1]; m_wg = fmaxf(m_wg, mw[w]); }
-      const float mu = (m_wg == -INFINITY) ? 0.f : m_wg;
-#pragma unroll
-      for (int w = 0; w < kPqvWaves; ++w) {
-        const float ww = __expf(mw[w] - mu);
-        if (tid < D) o_tot = fmaf(s_o[w][tid], ww, o_tot);
-        l_tot = fmaf(s_o[w][D], ww, l_tot);
-      }
-      m_run = m_wg;
-    }
+    static_assert(kPqvWaves == 4, "the fold of the waves' partials is written out for four");
+    const float m0 = s_o[0][D + 1], m1 = s_o[1][D + 1], m2 = s_o[2][D + 1], m3 = s_o[3][D + 1];
+    const float m_wg = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+    const float mu = (m_wg == -INFINITY) ? 0.f : m_wg;
+    const float w0 = __expf(m0 - mu), w1 = __expf(m1 - mu), w2 = __expf(m2 - mu), w3 = __expf(m3 - mu);
+    if (tid < D) o_tot = (s_o[0][tid] * w0 + s_o[1][tid] * w1) + (s_o[2][tid] * w2 + s_o[3][tid] * w3);
+    l_tot = (s_o[0][D] * w0 + s_o[1][D] * w1) + (s_o[2][D] * w2 + s_o[3][D] * w3);
+    m_run = m_wg;
   }
   T* outp = p.out + b * p.out_sb + h * D;
   // head importance: the MSB pass adds only for confident heads, the refetch pass for the heads it recomputes
@@ -562,8 +539,6 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
     __syncthreads();
     if (tid == 0 && commit) {
       float tot = (s_o[0][0] + s_o[0][1]) + (s_o[0][2] + s_o[0][3]);
-#pragma unroll
-      for (int w = 4; w < kPqvWaves; ++w) tot += s_o[0][w];
       p.head_abs[unit] += tot;
     }
   };
@@ -689,33 +664,30 @@ template <typename K> static int resident_capacity(K kernel) {
 }
 
 template <typename T, int D, int KB, int VB, bool SO = false>
-static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, int env_poll, hipStream_t st) {
+static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st) {
   const bool app = p.k_new != nullptr;
-  constexpr int UP = SPATTEN_PQV_UP;
+  constexpr int UP = kPqvUp;
   const dim3 grid((unsigned)p.S, (unsigned)n_active, (unsigned)p.B), blk(kPqvThreads);
   // (the pass-1 and pass-2 kernels of a profile have different register footprints: the smaller capacity decides)
   static const int cap_static = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, false, UP>),
                                          resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, false, UP>));
   static const int cap_dyn = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP>),
                                       resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP>));
-  p.poll_merge = (env_poll != 0 && p.S > 1 && (long long)p.S * n_active * p.B <= (dyn ? cap_dyn : cap_static)) ? 1 : 0;
+  p.poll_merge = (p.S > 1 && (long long)p.S * n_active * p.B <= (dyn ? cap_dyn : cap_static)) ? 1 : 0;
   // ---- the refetch pass (round 6): at the reference traces' rate 2-3 of 30 heads are flagged per layer-step; laid out like pass 1
   // their rows sit on S CUs each and the pass takes as long as if every head were flagged (a CU streams at ~21 B/ns).  So pass 2
   // gets its own, finer split-N (~256-row chunks, <= 64 splits) over a grid whose rows are the RANKS of the flagged heads: a few
   // flagged heads spread over the whole chip, unflagged rows of the grid exit at once.  The merge polls: workgroups are dispatched
   // in order, a head's merging (last) split after its siblings, and no other workgroup ever waits — safe beyond residency.
   PqvParams<T> p2 = p;
-  static int env_c = -1;
-  if (env_c < 0) { const char* e = getenv("SPATTEN_PQV_COMPACT"); env_c = e ? atoi(e) : 1; }
-  if (env_c && !msb_only && n_active <= 64) {
+  if (!msb_only && n_active <= 64) {
     const int lay = p.S * p.chunk;                       // the layout length pass 1 was laid out for
     const int ws_splits = (int)(p.ws_unit / (D + 2));
-    const int rows2 = env_c >= 64 ? env_c : 256;          // (SPATTEN_PQV_COMPACT=rows: A/B of the chunk length)
-    int S2 = std::min({kDecodeMaxSplits, ws_splits, std::max(p.S, ceil_div(lay, rows2))});
+    int S2 = std::min({kDecodeMaxSplits, ws_splits, std::max(p.S, ceil_div(lay, 256))});
     const int chunk2 = ceil_div(ceil_div(lay, S2), 8) * 8;
     S2 = ceil_div(lay, chunk2);
     p2.S = S2; p2.chunk = chunk2; p2.compact = 1; p2.n_act = n_active; p2.S1 = p.S; p2.chunk1 = p.chunk;
-    p2.poll_merge = (env_poll != 0 && S2 > 1) ? 1 : 0;
+    p2.poll_merge = S2 > 1 ? 1 : 0;
   }
   const dim3 grid2((unsigned)p2.S, (unsigned)n_active, (unsigned)p.B);
   // (SO: the scores-only kernels need no more registers than the full ones — the capacities above stay a safe bound)
@@ -748,8 +720,6 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
   const int chunk = ceil_div(ceil_div(lay, S), 8) * 8;
   S = ceil_div(lay, chunk);
   if (S > 1 && (!a->workspace || S > ws_splits)) return SPATTEN_ERR_INVALID;
-  static int env_poll = -1;
-  if (env_poll < 0) { const char* e = getenv("SPATTEN_DECODE_POLL"); env_poll = e ? atoi(e) : 1; }
   PqvParams<T> p;
   p.q = (const T*)a->q; p.q_sb = a->q_sb; p.q_sh = a->q_sh;
   p.pl = pd;
@@ -780,8 +750,8 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
   p.prev_lse = (lv && lv->acc) ? lv->prev_lse : a->lse; p.prev_len = (lv && lv->acc) ? lv->prev_len : 0;
   const bool dyn = a->step_state != nullptr, msb_only = (a->flags & SPATTEN_PQ_MSB_PASS_ONLY) != 0;
 #define SPATTEN_PQV(DD, KB, VB)                                                                     \
-  return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, env_poll, st)            \
-            : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, env_poll, st)
+  return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, st)            \
+            : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, st)
   if (d == 128) {
     if (kb == 4) SPATTEN_PQV(128, 4, 8);
     if (kb == 8) SPATTEN_PQV(128, 8, 8);

@@ -94,7 +94,7 @@ struct FlashParams {
   int64_t kv_sb, kv_sh;
   const T* vt;        // [B,Hkv,D,Npad]
   const T* v; int64_t v_sb, v_sh;   // the value cache itself [B,Hkv,>=N,D] (rows contiguous): read by the transposing
-                                    // LDS reads of the 128-key kernel at D = 128 (SPATTEN_PF_VTR), no Vt pre-pass
+                                    // LDS reads of the 128-key kernel at D = 128 (VTRP), no Vt pre-pass
   const T* mask; int64_t mask_sb, mask_sq;
   T* out; int64_t out_sb, out_sq;
   T* scores; int64_t sc_sb, sc_sh, sc_sq;
@@ -124,47 +124,18 @@ struct FlashParams {
   float* part_ml;     // [B*H*nqb][ksplit][256][2]
 };
 
-// A/B switches (tools/mb/pf_exp.sh rebuilds with -D<macro>=<v>; findings in DESIGN §3.4 and HISTORY.md).
-#ifndef SPATTEN_PF_PRIO         // static s_setprio for one half: MEASURED SLOWER (775-789 vs 812 TFLOP/s).  Off.
-#define SPATTEN_PF_PRIO 0
-#endif
-#ifndef SPATTEN_PF_EXPMODE      // harness bits: 1 = FASTNUM; 2 = no DMA in the tile loop and 8 = no softmax (both give WRONG
-#define SPATTEN_PF_EXPMODE 0    // results: anatomy only); 4 = DMA_MODE 2; 16 = no exp2 in the softmax (wrong results)
-#endif
-#ifndef SPATTEN_PF_DMA_MODE     // who issues a stage's LDS-DMA: 0 half 0 in its matrix / half 1 in its vector phase (r01, 762);
-#define SPATTEN_PF_DMA_MODE 2   // 1 both in their matrix phase (r02: 810 against 743 for 2); 2 both in their vector phase — r06, after the r05 softmax
-                                // diet: 2 is +1.5-2.4 % in both numerics (four alternations on two boxes: 882 / 991-1,022 against 870 / 973-998 TFLOP/s);
-                                // 3 = K pieces from the matrix, V pieces from the vector phase: as 1
-#endif
 // FAST (template flag of prefill_pp128_kernel; run-time opt-in SPATTEN_PREFILL_FAST_NUMERICS of spatten_attn_prefill):
 // logits kept in fp32 — no reference roundings (matmul -> dtype, / sqrt(d) -> dtype) — with the scale folded into the
 // exponent: -384 of ~609 VALU per wave-tile.  NOT the default: the flash kernel's logits stay the reference's (DESIGN
-// §3.4).  The harness bit SPATTEN_PF_EXPMODE & 1 forces it for every launch (anatomy builds).
+// §3.4).
 // VTRP (template flag of prefill_pp128_kernel, d = 128): the V operand of P.V straight from the value rows — the tile is
 // DMA-ed row-major ([128 keys][D]) and read with ds_read_b64_tr_b16 (gfx950's transposing LDS read), so the launch needs no
 // key-contiguous copy of V (the vt_kernel pre-pass: 9 of the 36 us of the 64-token turn prefill).  Two 8-byte transposing
 // reads per fragment instead of one 16-byte read make the flash kernel itself slower, so the form is chosen per shape
-// (use_vtr below); SPATTEN_PREFILL_VTR=0|1 forces it (A/B).
-#ifndef SPATTEN_PF_VTR_MAXQ
-#define SPATTEN_PF_VTR_MAXQ 512  // transposing reads for query blocks up to this length
-#endif
-#ifndef SPATTEN_PF_LOCKSTEP      // A/B: both halves in the same phase (no ping-pong offset) — with DMA_MODE 1 both issue their pieces of
-#define SPATTEN_PF_LOCKSTEP 0    // stage t+1 at the top of the matrix phase and wait for them at the end of the vector phase
-#endif
-#ifndef SPATTEN_PF_P1            // the reference roundings of S(t+1) behind the wave's own P.V MFMAs (prefill_pp128_kernel)
-#define SPATTEN_PF_P1 0
-#endif
-#ifndef SPATTEN_PF_ROWSUM_MFMA  // row sums of P on the matrix pipe instead of 64 VALU adds per lane and tile: MEASURED SLOWER
-#define SPATTEN_PF_ROWSUM_MFMA 0   // (713 vs 768): the 8 extra MFMAs per tile cost more than the adds they replace.  Off.
-#endif
-#ifndef SPATTEN_PF_DIET         // r05 A/B switches of prefill_pp128_kernel's softmax (bits; prebuilt variants: tools/mb/build_variant.sh):
-#define SPATTEN_PF_DIET 0       //   2 = no per-tile maximum on fully visible tiles (exponentials against the running maximum, the lane's
-#endif                          //       sum bounds every one of them; the rare tile that outgrows it is redone): parity-green, MEASURED
-                                //       NEUTRAL-TO-SLOWER (824-831 vs 841-850 TFLOP/s at q = N = 8192, alternating in one call) — off;
-                                //   4 = row sums of the ROUNDED P on the packed-dot unit: slower (785; v_dot2 costs ~2.4 plain issues)
+// (use_vtr_for below).
+constexpr int kPfVtrMaxQ = 512;  // transposing reads for query blocks up to this length
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kDeferMax = 8.0f;   // natural-log units of the scaled logits
-constexpr float kSumBound = 2980.0f;   // < e^kDeferMax: a lane whose 64 exponentials sum to no more holds none above e^kDeferMax
 
 // A row whose every logit so far is a mask value (HF's finfo.min added, then rounded: all equal to the maximum) weighs those
 // keys equally, as the reference's softmax does.  Its exponent m * log2e overflows fp32 (|finfo.min| * log2e > FLT_MAX), and
@@ -563,7 +534,7 @@ __global__ __launch_bounds__(512, 1) void prefill_pp_kernel(const FlashParams<T>
       if (next_stage < n_tiles) load_stage(next_stage);
     }
     PF_STAMP(3);
-    if (!(SPATTEN_PF_EXPMODE & 8) && t + 1 < wave_tiles) softmax_tile(t + 1);
+    if (t + 1 < wave_tiles) softmax_tile(t + 1);
     PF_STAMP(4);
     __syncthreads();
     PF_STAMP(5);
@@ -613,12 +584,10 @@ template <int ROWB> __device__ inline int swz_slot(int row, int p) {   // logica
 
 template <typename T, int D, bool MASK, int PQK = 0, bool FASTN = false, bool VTRP = false, bool PAIR = false>
 __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams<T> p) {
-  constexpr bool FAST = FASTN || (SPATTEN_PF_EXPMODE & 1);
+  constexpr bool FAST = FASTN;
   // (P1 is neutral in the two-half ping-pong — 8192: 691 vs 679 us — and pays where a half runs ALONE, i.e. in the paired form's
   //  solo steps: q = N = 2048 71.2 -> 67.7 us; lock-step halves instead of the ping-pong: 774 us at 8192, 728 with P1)
-  constexpr bool P1 = (SPATTEN_PF_P1 || PAIR) && !FAST && PQK == 0 && !MASK;
-  constexpr bool NOMAX = (SPATTEN_PF_DIET & 2) && PQK == 0;      // (pass 1 of the quantised keys tracks the row's TRUE maximum)
-  constexpr bool DOTSUM = (SPATTEN_PF_DIET & 4) && DT<T>::k16;
+  constexpr bool P1 = PAIR && !FAST && PQK == 0 && !MASK;
   constexpr int KT = 128, NKB = KT / 32;                      // keys per tile, 32-key blocks per tile
   constexpr int KK = D / 16, DB = D / 32, KROWB = D * 2;
   constexpr int KBYTES = KT * KROWB, VBYTES = D * 256, BUF = KBYTES + VBYTES;   // Vt row = 128 keys = 256 B
@@ -736,16 +705,8 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
-  // Row sums on the MATRIX pipe (SPATTEN_PF_ROWSUM_MFMA): O^T = Vt . P^T gets one more 32-row block whose row 0 is all
-  // ones — an A operand that lives in registers — so accumulator register 0 of lanes 0-31 IS sum_keys P for the lane's
-  // query.  8 extra MFMAs per 128-key tile (the matrix pipe has the slack) replace 64 VALU adds per lane (the vector
-  // phase is the pole), and the sum is taken over the SAME rounded P that multiplies V.
-  f32x16 osum;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) osum[r] = 0.f;
-  frag ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = DT<T>::from_f32(qi == 0 ? 1.f : 0.f);
+  // (row sums of P on the matrix pipe — one more 32-row block of O^T = Vt . P^T whose A operand is a row of ones — instead of 64
+  //  VALU adds per lane and tile measured slower, 713 vs 768 TFLOP/s: the 8 extra MFMAs per tile cost more than the adds)
   float m_true = -INFINITY;   // PQK == 1: the row's TRUE running maximum (m_run may lag it: deferred rescale)
 
   const int wg_q_end = PQK == 2 ? blkend_l : min(p.q_len, paired ? (2 * nqb - qblk) * 128 : qblk * 256 + 256);   // (paired: the end of the LATER block)
@@ -828,15 +789,10 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
     if (j + 1 < n_tiles) dma_k(j + 1, k_area(j));
     if (j < n_att_tiles) dma_v(j, v_area(j));
   };
-  [[maybe_unused]] auto dma_stage_k = [&](int j) { if (j + 1 < n_tiles) dma_k(j + 1, k_area(j)); };   // (DMA_MODE 3: the stage's two halves
-  [[maybe_unused]] auto dma_stage_v = [&](int j) { if (j < n_att_tiles) dma_v(j, v_area(j)); };       //  go out in different phases)
 
   f32x16 s[NKB];
   frag pf[NKB][2];
-#ifndef SPATTEN_PF_RING
-#define SPATTEN_PF_RING 4
-#endif
-  constexpr int RING = SPATTEN_PF_RING;
+  constexpr int RING = 4;
   auto qk = [&](const char* kbuf) {
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb)
@@ -906,9 +862,6 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
       const int db = i % DB, kt = i / DB;
       o[db] = Mfma<T>::mma(a[i % RING], pf[kt >> 1][kt & 1], o[db]);
       if (i + RING < 2 * NKB * DB) a[i % RING] = vfrag(i + RING);
-#if SPATTEN_PF_ROWSUM_MFMA
-      if (db == DB - 1) osum = Mfma<T>::mma(ones, pf[kt >> 1][kt & 1], osum);
-#endif
       if constexpr (WP1) {      // 2 * NKB * DB MFMAs, NKB * 8 logit pairs: pairs_per logit pairs behind each MFMA
         constexpr int pairs_per = (NKB * 8) / (2 * NKB * DB) > 0 ? (NKB * 8) / (2 * NKB * DB) : 1;
 #pragma unroll
@@ -932,7 +885,7 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
         __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
       }
     } else {
-      __builtin_amdgcn_sched_group_barrier(0x008, RING + (SPATTEN_PF_ROWSUM_MFMA ? 2 * NKB : 0), 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, RING, 0);
     }
   };
 
@@ -982,22 +935,10 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-#if SPATTEN_PF_EXPMODE & 16      // anatomy: what do the 64 transcendentals per wave-tile cost?  (WRONG results)
-            const float pvv = fmaf(s[kb][t * 8 + e], sc2, -m2);
-#else
             const float pvv = __builtin_amdgcn_exp2f(fmaf(s[kb][t * 8 + e], sc2, -m2));
-#endif
-#if !SPATTEN_PF_ROWSUM_MFMA
-            if (!DOTSUM) ls[e & 3] += pvv;
-#endif
+            ls[e & 3] += pvv;
             pf[kb][t][e] = DT<T>::from_f32(pvv);
           }
-#if !SPATTEN_PF_ROWSUM_MFMA
-          if constexpr (DOTSUM) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ls[j] = pair_sum<T>(reinterpret_cast<const uint32_t*>(&pf[kb][t])[j], ls[j]);
-          }
-#endif
         }
       return (ls[0] + ls[1]) + (ls[2] + ls[3]);
     };
@@ -1018,25 +959,13 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
       // e^kDeferMax, which bf16 P (constant relative precision) and the fp32 sums carry without loss.  O / l is
       // mathematically unchanged.  All of the previous tile's P·V is already in O (matrix phase, program order), so
       // the decision covers it.
-      if constexpr (NOMAX) {
-        // r05: no maximum at all on the common path (32 v_max3 + the exchange per tile).  The exponentials are taken against
-        // the running maximum as it stands; the lane's sum of its 64 bounds every one of them, so "sum <= kSumBound" proves
-        // that none outgrew e^kDeferMax — the deferred rule's own condition.  Otherwise (first tile: m_run = -inf gives
-        // inf; an outlier key; NaN) the tile is redone against its true maximum: P and the sum are overwritten, nothing of
-        // the first pass survives.
-        m_new = m_run;
-        lsum = exp_pass(m_run);
-        if (__builtin_amdgcn_ballot_w64(!(lsum <= kSumBound)) != 0) {
-          m_new = fmaxf(m_run, tile_max());
-          lsum = exp_pass(m_new);
-        }
-      } else {
-        const float m_tile = tile_max();
-        const bool move = __builtin_amdgcn_ballot_w64(m_tile - m_run > kDeferMax) != 0;   // -inf start: inf > thr
-        m_new = move ? fmaxf(m_run, m_tile) : m_run;
-        if (PQK == 1) m_true = fmaxf(m_true, m_tile);
-        lsum = exp_pass(m_new);
-      }
+      // (r05, measured neutral-to-slower and dropped: no per-tile maximum at all on this path — exponentials against the running
+      //  maximum, the tile redone when the lane's sum shows one outgrew it: 824-831 vs 841-850 TFLOP/s at q = N = 8192)
+      const float m_tile = tile_max();
+      const bool move = __builtin_amdgcn_ballot_w64(m_tile - m_run > kDeferMax) != 0;   // -inf start: inf > thr
+      m_new = move ? fmaxf(m_run, m_tile) : m_run;
+      if (PQK == 1) m_true = fmaxf(m_true, m_tile);
+      lsum = exp_pass(m_new);
       m_shift = (m_new == -INFINITY) ? 0.f : m_new;
     } else {
       // explicit mask and / or a tile that straddles the causal diagonal: per-element visibility
@@ -1063,7 +992,6 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
     if (m_new != m_run) {
       const float alpha = __expf(m_run - m_shift);
       l_run *= alpha;
-      osum[0] *= alpha;
 #pragma unroll
       for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -1084,33 +1012,12 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
   if (wave_tiles > T0) softmax_tile(T0);
   __builtin_amdgcn_s_waitcnt(0x0F70);
   __syncthreads();
-  if (!SPATTEN_PF_LOCKSTEP && grp == 1) __syncthreads();                     // hold half 1 one phase behind
+  if (grp == 1) __syncthreads();                     // hold half 1 one phase behind
 
-#if SPATTEN_PF_PRIO == 1
-  if (grp == 1) __builtin_amdgcn_s_setprio(1);   // static priority for the later-dispatched half (A/B knob)
-#elif SPATTEN_PF_PRIO == 2
-  if (grp == 0) __builtin_amdgcn_s_setprio(1);
-#endif
+  // (a static s_setprio for either half measured slower: 775-789 vs 812 TFLOP/s)
   for (int t = T0; t < n_tiles; ++t) {
     // ---- matrix phase of iteration t -----------------------------------------------------------------------
     PF_STAMP(0);
-#if SPATTEN_PF_DMA_MODE == 1
-    // BOTH halves bring their pieces of stage t+1 in at the top of their own matrix phase, where the ~115 cycles each DMA
-    // instruction takes to issue hide under the MFMAs (phase stamps, r02: issued from the vector phase, half 1's 16 DMA
-    // instructions cost 1.8k cycles on top of its 3.5k-cycle softmax, and half 0 idled 1.8k cycles at the barrier every
-    // tile).  Half 0 issues in global phase 2t and has the whole following vector phase for them to land; half 1 issues
-    // in phase 2t+1 and waits for them at the end of that same phase (stage t+1 is first read in phase 2t+2).  The
-    // slot's previous tenant, stage t-1, was last read in phase 2t-1.
-    if (!(SPATTEN_PF_EXPMODE & 2) && t >= T0 + 1 && t + 1 < n_tiles) dma_stage(t + 1);
-    PF_STAMP(6);           // (the stage's LDS-DMA pieces issued)
-#elif SPATTEN_PF_DMA_MODE == 0
-    if (grp == 0 && t >= T0 + 1 && t + 1 < n_tiles) dma_stage(t + 1);
-#elif SPATTEN_PF_DMA_MODE == 3
-    // round 6: the stage's K pieces from the matrix phase (as mode 1), its V pieces from the vector phase (as mode 2): four DMA
-    // instructions per wave in each phase instead of eight in one — each costs ~115-125 cycles of the wave's issue whichever phase
-    // it sits in, and the phase that carries all eight is the longer one of the step (matrix phase in fast numerics)
-    if (!(SPATTEN_PF_EXPMODE & 2) && t >= T0 + 1 && t + 1 < n_tiles) dma_stage_k(t + 1);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     bool rounded = false;
     if constexpr (P1) {
@@ -1130,36 +1037,27 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
     }
     PF_STAMP(1);
 
-    if (!SPATTEN_PF_LOCKSTEP && grp == 1) __builtin_amdgcn_s_waitcnt(0x0F70);    // half 1's pieces (issued one phase ago) have landed
+    if (grp == 1) __builtin_amdgcn_s_waitcnt(0x0F70);    // half 1's pieces (issued one phase ago) have landed
     __syncthreads();
     PF_STAMP(2);
     // ---- vector phase ----------------------------------------------------------------------------------------
-#if SPATTEN_PF_DMA_MODE == 0
-    if (grp == 1 && t + 2 < n_tiles) dma_stage(t + 2);
-#elif SPATTEN_PF_DMA_MODE == 2
-    // both halves issue from their VECTOR phase (stage t+1 may be written during global phases 2t and 2t+1: half 1 is in
-    // its vector phase of iteration t-1 during 2t, half 0 in its vector phase of iteration t during 2t+1)
+    // both halves issue their LDS-DMA from their VECTOR phase (stage t+1 may be written during global phases 2t and 2t+1: half 1
+    // is in its vector phase of iteration t-1 during 2t, half 0 in its vector phase of iteration t during 2t+1).  r06, after the r05
+    // softmax diet: +1.5-2.4 % in both numerics against both halves issuing from their matrix phase (882 / 991-1,022 against
+    // 870 / 973-998 TFLOP/s); K pieces from the matrix and V pieces from the vector phase: as the matrix phase
     if (grp == 0 && t >= T0 + 1 && t + 1 < n_tiles) dma_stage(t + 1);
     if (grp == 1 && t + 2 < n_tiles) dma_stage(t + 2);
-#elif SPATTEN_PF_DMA_MODE == 3
-    if (grp == 0 && t >= T0 + 1 && t + 1 < n_tiles) dma_stage_v(t + 1);
-    if (grp == 1 && t + 2 < n_tiles) dma_stage_v(t + 2);
-#endif
     PF_STAMP(3);
-    if (!(SPATTEN_PF_EXPMODE & 8) && t + 1 < wave_tiles) softmax_tile(t + 1, rounded);
+    if (t + 1 < wave_tiles) softmax_tile(t + 1, rounded);
     PF_STAMP(4);
-    if (SPATTEN_PF_LOCKSTEP || grp == 0) __builtin_amdgcn_s_waitcnt(0x0F70);    // half 0's pieces (issued at the top of this iteration)
+    if (grp == 0) __builtin_amdgcn_s_waitcnt(0x0F70);    // half 0's pieces (issued at the top of this iteration)
     __syncthreads();
     PF_STAMP(5);
   }
-  if (!SPATTEN_PF_LOCKSTEP && grp == 0) __syncthreads();
+  if (grp == 0) __syncthreads();
 
   // ---- epilogue: O = O^T / l, 4 consecutive dv per 8-byte store ---------------------------------
-#if SPATTEN_PF_ROWSUM_MFMA
-  const float l_tot = xor32_sum(hi == 0 ? osum[0] : 0.f);     // register 0 of lanes 0-31 = row 0 of the ones block
-#else
   const float l_tot = xor32_sum(l_run);
-#endif
   if (ks_eff > 1) {       // partial result of this key range: un-normalised O^T, (m, l) — folded by prefill_merge_kernel
     const int64_t slot = ((int64_t)item * ksplit + ks) * 256 + wave * 32 + qi;
     float* po = p.part_o + slot * D;
@@ -1184,10 +1082,7 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
     const float pmax = __expf(m_true - m_run) * inv;
     if (qvalid && hi == 0) p.need[(int64_t)(b * p.H + h) * p.q_len + myq] = pmax < p.pq_thr ? 1 : 0;
   }
-#ifndef SPATTEN_PF_ROWSTORE    // 1: O staged through LDS and stored as whole rows (A/B: tools/mb/pf_exp.sh SPATTEN_PF_ROWSTORE 0 1)
-#define SPATTEN_PF_ROWSTORE 1
-#endif
-  if (SPATTEN_PF_ROWSTORE && PQK != 2 && D == 128) {
+  if (PQK != 2 && D == 128) {
     // Whole rows: the accumulator layout gives a lane 4 consecutive dv of ONE query row per store — 16 eight-byte stores per
     // lane at a row stride, 32-64 lines touched by every wave instruction; the epilogue of a 256-row block then costs ~9k
     // cycles of store issue (a tile is ~8k: 13 % of a q = N = 2048 block).  All tile traffic is over (the barrier above), so
@@ -1458,40 +1353,28 @@ static inline int rows_splits(int units) { int s = 256 / (units > 0 ? units : 1)
 
 // Kernel choice.  No by-products (the prefill of the multi-turn protocol, the bench): 128-key tiles + LDS-DMA.  With a
 // stash / column-importance output the softmax phase carries the extra stores and reductions, and the 64-key kernel
-// (half the live scores per lane) is the one that stays out of scratch.  SPATTEN_PREFILL_VARIANT=1 forces the 64-key
-// kernel everywhere (A/B measurements).
-static int prefill_variant() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("SPATTEN_PREFILL_VARIANT"); v = e ? atoi(e) : 0; if (v < 0 || v > 1) v = 0; }
-  return v;
-}
+// (half the live scores per lane) is the one that stays out of scratch.
 
 // Transposing-read form of the 128-key kernel (no Vt pre-pass): when the pre-pass — all kv_len keys, whatever q_len — is
 // a large part of the launch, i.e. a short query block on a long cache.
 static inline bool use_vtr_for(int head_dim, int q_len, int kv_len) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("SPATTEN_PREFILL_VTR"); env = e ? atoi(e) : 2; }   // 0 off, 1 on, 2 by shape
-  if (head_dim != 128 || env == 0) return false;
-  if (env == 1) return true;
-  // measured (tools/probe_vtr.py, H = 32, us per layer, Vt form | transposing reads): q = 64 on 2112: 36.2 | 28.7; 256 on
+  if (head_dim != 128) return false;
+  // measured (H = 32, us per layer, Vt form | transposing reads): q = 64 on 2112: 36.2 | 28.7; 256 on
   // 2304: 44.3 | 37.5; 512 on 2560: 56.9 | 51.2; 1024 on 2048: 76.8 | 81.1; 1024 on 4096: 132.5 | 149.3; 2048 on 2048:
   // 79.9 | 83.5; 4096 on 4096: 246 | 265 — the pre-pass costs ~9 us per 2k keys, the two-read fragments ~7 % of the flash time
   // (r04, paired blocks: a first prompt of 1024 tokens — q = N = 1024 — 40.3 | 37.7; 2048 on 2048 68.4 | 68.6;
   //  r05, after the softmax diet: q = N = 1024 39.4 | 35.7, 1536 52.7 | 49.4, 2048 66.3 | 64.1, 2560 104.1 | 101.7, 3072 144.0 |
   //  155.0; 1024 on 2048 68.2 | 69.4, 2048 on 4096 148.4 | 148.4 — a whole prompt up to 2560 tokens takes the transposing reads)
-  return q_len <= SPATTEN_PF_VTR_MAXQ || (q_len == kv_len && q_len <= 5 * SPATTEN_PF_VTR_MAXQ);
+  return q_len <= kPfVtrMaxQ || (q_len == kv_len && q_len <= 5 * kPfVtrMaxQ);
 }
 
 
 // Key split of the plain flash kernel: only when the launch would leave most of the chip idle (few query blocks x heads)
 // and every range still has >= 2 key tiles.  The same rule sizes the workspace.
 static inline int flash_ksplit(int batch, int heads, int q_len, int kv_len) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("SPATTEN_PREFILL_KSPLIT"); env = e ? atoi(e) : 0; }   // 1 = off, n = forced (A/B)
   const long long items = (long long)batch * heads * ceil_div(q_len, 256);
   const int tiles = ceil_div(kv_len, 128);
   int ks = (items >= 128 || tiles < 8) ? 1 : (int)(256 / items);    // short key ranges: the partials cost more than they buy
-  if (env > 0) ks = env;
   if (ks > 8) ks = 8;
   if (ks > tiles / 2) ks = tiles / 2;
   if (ks < 1) ks = 1;
@@ -1500,13 +1383,11 @@ static inline int flash_ksplit(int batch, int heads, int q_len, int kv_len) {
 }
 // paired 128-row blocks (prefill_pp128_kernel<..., PAIR>): a causal block of whole 256-row groups whose workgroups all fit the chip at once
 static inline bool flash_pair(int batch, int heads, int q_len, int causal) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("SPATTEN_PREFILL_PAIR"); env = e ? atoi(e) : 2; }   // 0 = off, 1 = forced (A/B), 2 = auto
-  if (!causal || q_len % 256 != 0 || q_len < 512 || env == 0) return false;
+  if (!causal || q_len % 256 != 0 || q_len < 512) return false;
   // (r05: also when the 256-row blocks are exactly TWO per CU — q = N = 4096 at 32 heads 235.6 -> 226.2 us, 4096 on 8192 525 -> 519;
   //  320 workgroups (2560 tokens) 103 -> 122, 640 / 768 / 1024: slower — the dispatch order balances those by itself)
   const long long items = (long long)batch * heads * (q_len / 256);
-  return env == 1 || items <= 256 || items == 512;
+  return items <= 256 || items == 512;
 }
 static inline size_t flash_partial_bytes(int batch, int heads, int head_dim, int q_len, int ks) {
   if (ks <= 1) return 0;
@@ -1516,10 +1397,8 @@ static inline size_t flash_partial_bytes(int batch, int heads, int head_dim, int
 // key ranges of the refetch pass of the quantised-key prefill: >= 8 tiles of 128 keys each, at most 8 ranges (the kernel falls
 // back to ONE range by itself when more than a quarter of the rows were flagged: a long list fills the chip without splitting)
 static inline int pq_pass2_ksplit(int kv_len) {
-  static int env = -1;
-  if (env < 0) { const char* e = getenv("SPATTEN_PQ_PASS2_KSPLIT"); env = e ? atoi(e) : 0; }     // 1 = off (A/B)
   const int tiles = ceil_div(kv_len, 128);
-  int ks = env > 0 ? env : tiles / 8;
+  int ks = tiles / 8;
   if (ks > 8) ks = 8;
   if (ks < 1) ks = 1;
   const int per = ceil_div(tiles, ks);
@@ -1543,20 +1422,18 @@ static void launch_flash_m(const FlashParams<T>& p, hipStream_t st) {
       }
       return;
     }
-    if (prefill_variant() == 0) {
-      const dim3 gridk((unsigned)(p.nqb * p.H * p.B * (p.ksplit > 1 ? p.ksplit : 1)));
-      if (p.mask) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, true>), gridk, dim3(512), 0, st, p);
-      else if (p.fast) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, true>), gridk, dim3(512), 0, st, p);
-      else if (p.pair && p.vtr) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, false, true, true>), gridk, dim3(512), 0, st, p);
-      else if (p.pair) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, false, false, true>), gridk, dim3(512), 0, st, p);
-      else if (p.vtr) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, false, true>), gridk, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false>), gridk, dim3(512), 0, st, p);
-      if (p.ksplit > 1) {
-        const long long rows = (long long)p.B * p.H * p.q_len;
-        hipLaunchKernelGGL((prefill_merge_kernel<T, D>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p);
-      }
-      return;
+    const dim3 gridk((unsigned)(p.nqb * p.H * p.B * (p.ksplit > 1 ? p.ksplit : 1)));
+    if (p.mask) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, true>), gridk, dim3(512), 0, st, p);
+    else if (p.fast) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, true>), gridk, dim3(512), 0, st, p);
+    else if (p.pair && p.vtr) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, false, true, true>), gridk, dim3(512), 0, st, p);
+    else if (p.pair) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, false, false, true>), gridk, dim3(512), 0, st, p);
+    else if (p.vtr) hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false, 0, false, true>), gridk, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((prefill_pp128_kernel<T, D, false>), gridk, dim3(512), 0, st, p);
+    if (p.ksplit > 1) {
+      const long long rows = (long long)p.B * p.H * p.q_len;
+      hipLaunchKernelGGL((prefill_merge_kernel<T, D>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p);
     }
+    return;
   }
   if (p.mask) hipLaunchKernelGGL((prefill_pp_kernel<T, D, ST, CI, true>), grid, dim3(512), 0, st, p);
   else hipLaunchKernelGGL((prefill_pp_kernel<T, D, ST, CI, false>), grid, dim3(512), 0, st, p);
@@ -1654,9 +1531,9 @@ extern "C" int spatten_attn_prefill(int dtype, const void* q, int64_t q_sb, int6
   const int npad = ceil_div(kv_len, 128) * 128;      // Vt rows padded to whole 128-key tiles (zeros beyond kv_len)
   void* vt = ws;
   // (1) the queries are rotated inside the flash kernel (its prologue)
-  // (2) key-contiguous V — only for the kernels that still read it: the 64-key kernel (stash / column-importance outputs,
-  // SPATTEN_PREFILL_VARIANT=1) and d = 64; the 128-key kernel at d = 128 reads the value rows themselves (SPATTEN_PF_VTR)
-  const bool use_vtr = use_vtr_for(head_dim, q_len, kv_len) && !scores && !col_importance && !mask && prefill_variant() == 0 &&
+  // (2) key-contiguous V — only for the kernels that still read it: the 64-key kernel (stash / column-importance outputs)
+  // and d = 64; the 128-key kernel at d = 128 reads the value rows themselves (use_vtr_for)
+  const bool use_vtr = use_vtr_for(head_dim, q_len, kv_len) && !scores && !col_importance && !mask &&
                        !(causal & SPATTEN_PREFILL_FAST_NUMERICS);
   if (!use_vtr) {
     const dim3 grid((unsigned)(npad / 64), (unsigned)kv_heads, (unsigned)batch);
@@ -1683,10 +1560,10 @@ extern "C" int spatten_attn_prefill(int dtype, const void* q, int64_t q_sb, int6
     p.B = batch; p.H = heads; p.Hkv = kv_heads; p.q_len = q_len; p.N = kv_len; p.Npad = npad;          \
     p.causal = causal & 1; p.fast = (causal & SPATTEN_PREFILL_FAST_NUMERICS) != 0 && !scores && !col_importance && !lse; \
     p.sqrt_d = sqrtf((float)head_dim); p.nqb = ceil_div(q_len, 256);                                   \
-    p.ksplit = (!scores && !col_importance && prefill_variant() == 0) ? flash_ksplit(batch, heads, q_len, kv_len) : 1; \
+    p.ksplit = (!scores && !col_importance) ? flash_ksplit(batch, heads, q_len, kv_len) : 1; \
     p.part_o = (float*)(ws + align256((size_t)batch * kv_heads * head_dim * npad * 2));                \
     p.part_ml = p.part_o + (size_t)batch * heads * p.nqb * p.ksplit * 256 * head_dim;                   \
-    p.pair = flash_pair(batch, heads, q_len, causal & 1) && p.ksplit == 1 && !scores && !col_importance && !mask && !p.fast && prefill_variant() == 0; \
+    p.pair = flash_pair(batch, heads, q_len, causal & 1) && p.ksplit == 1 && !scores && !col_importance && !mask && !p.fast; \
     return launch_flash<T, DD>(p, st);                                                                 \
   }
   if (dtype == SPATTEN_BF16) { if (head_dim == 128) SPATTEN_FLASH(bf16_t, 128) else SPATTEN_FLASH(bf16_t, 64) }

@@ -110,9 +110,6 @@ __global__ __launch_bounds__(NT) void topk_select_reg_kernel(const SelectParams<
   const int jmax = (W + NT - 1) / NT;    // registers j >= jmax are padding in every thread: skipped below
   if (tid < 6) (&s_tot[0][0])[tid] = 0u;
   __syncthreads();
-#if defined(SPATTEN_SEL_EXP) && SPATTEN_SEL_EXP == 1
-  { unsigned x = 0; for (int j = 0; j < VPT; ++j) x ^= key[j]; if (x == 0x12345u) out[0] = 1; return; }
-#endif
 
   unsigned t = 0;
   int pass = 0;
@@ -145,9 +142,6 @@ __global__ __launch_bounds__(NT) void topk_select_reg_kernel(const SelectParams<
     const unsigned t0 = s_tot[slot][0], n3 = s_tot[slot][1], n1 = t0 & 0xFFFFu, n2 = t0 >> 16;
     t |= (n3 >= k ? 3u : (n2 >= k ? 2u : (n1 >= k ? 1u : 0u))) << s;
   }
-#if defined(SPATTEN_SEL_EXP) && SPATTEN_SEL_EXP == 2
-  { if (t == 0x12345u) out[0] = 1; return; }
-#endif
   // t = key of the k-th largest.  Order-preserving compaction: packed (greater, equal) counts per cell, one scan over
   // the cells, lane offsets from the ballots.
 #pragma unroll
@@ -174,9 +168,6 @@ __global__ __launch_bounds__(NT) void topk_select_reg_kernel(const SelectParams<
   }
   __syncthreads();
   const unsigned need_eq = k - (s_cell[NE] >> 16);      // >= 1: that many keys equal to t are kept, lowest index first
-#if defined(SPATTEN_SEL_EXP) && SPATTEN_SEL_EXP == 3
-  { if (need_eq == 0x12345u) out[0] = 1; return; }
-#endif
 #pragma unroll
   for (int j = 0; j < VPT; ++j) {
     const int i = j * NT + tid;
@@ -378,15 +369,13 @@ static int launch_select(const void* score, const void* const* score_ptrs, int64
   p.score = (const T*)score; p.score_ptrs = score_ptrs; p.score_sh = score_sh;
   p.idx = idx; p.idx_sl = idx_sl; p.idx_sh = idx_sh;
   p.H = H; p.lo = lo; p.hi = hi; p.k = k;
-  static int env_fast = -1;
-  if (env_fast < 0) { const char* e = getenv("SPATTEN_SELECT_REG"); env_fast = e ? atoi(e) : 1; }
   const int W = hi - lo;
   const dim3 grid((unsigned)(layers * H));
   // Many windows (the prune event: layers x heads of them): 4-wave workgroups, several resident per CU, cheap barriers.
   // Few long windows (local V pruning: one per head): 16 waves on one window.
   const bool many = layers * H >= 128;
 #define SPATTEN_SEL(NT_, VPT_) hipLaunchKernelGGL((topk_select_reg_kernel<T, NT_, VPT_>), grid, dim3(NT_), 0, st, p)
-  if (!env_fast || W > 32768) hipLaunchKernelGGL((topk_select_kernel<T>), grid, dim3(kSelThreads), 0, st, p);
+  if (W > 32768) hipLaunchKernelGGL((topk_select_kernel<T>), grid, dim3(kSelThreads), 0, st, p);
   else if (W <= 1024) SPATTEN_SEL(256, 4);
   else if (many && W <= 4096) SPATTEN_SEL(256, 16);
   else if (many && W <= 8192) SPATTEN_SEL(256, 32);

@@ -1,6 +1,6 @@
 # Build a variant of the library HERE (no GPU needed) for an A/B on the GPU box: one translation unit recompiled with extra
 # flags, the rest taken from build/ (run `make -j8 lib` first).  The .so travels with the snapshot (git-ignored).
-#   bash tools/mb/build_variant.sh NAME prefill_attn "-DSPATTEN_PF_DIET=0"      -> tools/mb/ab/lib_NAME.so
+#   bash tools/mb/build_variant.sh NAME prefill_attn "-DSPATTEN_PF_TRACE"      -> tools/mb/ab/lib_NAME.so
 #   bash tools/mb/pf_ab_lib.sh tools/mb/ab/lib_A.so tools/mb/ab/lib_B.so        (on the box)
 set -e
 cd "$(dirname "$0")/../.."

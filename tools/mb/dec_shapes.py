@@ -1,5 +1,5 @@
 """The plain decode step at several shapes (B = 1, bf16, d = 128), one HIP graph over rotating layers, us per layer:
-   python tools/mb/dec_shapes.py        (SPATTEN_DECODE_TEAM=256|512, SPATTEN_DECODE_TEAM_PIPE=0|1 select the team)"""
+   python tools/mb/dec_shapes.py        (SPATTEN_DECODE_TEAM=256|512 selects the team)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

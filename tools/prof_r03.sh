@@ -22,6 +22,5 @@ done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_pg -o pg -- python $R/tools/probe_plugin_graph.py 111 > $O/r03_plugin_graph_probe.txt 2>&1
 python $R/tools/trim_stats.py $(find $O/prof_pg -name "*kernel_stats.csv" | head -1) $O/r03_plugin_graph_kernel_stats.csv
 head -6 $O/r03_plugin_graph_kernel_stats.csv | cut -c1-200
-# decode anatomy: the shipped kernel, without the split merge, without the in-workgroup reduction (wrong results: timing only)
-cd $R && bash tools/mb/dec_exp.sh "" "-DSPATTEN_EXP_NOMERGE" "-DSPATTEN_EXP_NOREDUCE" > $O/r03_decode_anatomy_ab.txt 2>&1
-cat $O/r03_decode_anatomy_ab.txt
+# (r03_decode_anatomy_ab.txt — the decode kernel without the split merge / without the in-workgroup reduction — came from two stripped
+#  builds whose switches left the kernel with the experiments: `git show bb70390:tools/prof_r03.sh`)
