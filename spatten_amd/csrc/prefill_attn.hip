@@ -976,7 +976,20 @@ __global__ __launch_bounds__(512, 1) void prefill_pp128_kernel(const FlashParams
         for (int r = 0; r < 16; ++r) {
           float v = s[kb][r];
           const int key = tile * KT + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if (MASK) { if (key < p.N) v = DT<T>::round(v + DT<T>::to_f32(maskrow[key])); }   // :132
+          if (MASK) {
+            if (key < p.N) {
+              const float mv = DT<T>::to_f32(maskrow[key]);
+              if (PQK) {
+                // quantised keys: the logits stay fp32 under a mask too (include/spatten.h; the sum rounded to the model
+                // dtype moved the refetch flag by a 16-bit ulp of the logit).  A hard-masked key (finfo.min) sits AT finfo.min,
+                // so that a row without any other key still weighs them equally (masked_row_shift)
+                constexpr float kFinfoMin = DT<T>::kId == SPATTEN_F16 ? -65504.0f : -3.3895313892515355e38f;
+                v = mv <= 0.5f * kFinfoMin ? kFinfoMin : v + mv;
+              } else {
+                v = DT<T>::round(v + mv);   // :132
+              }
+            }
+          }
           v = (key < my_vis) ? v : -INFINITY;
           s[kb][r] = v;
           m_tile = fmaxf(m_tile, v);
