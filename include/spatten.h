@@ -688,6 +688,49 @@ typedef struct spatten_pq_local_v_args {
 size_t spatten_pq_local_v_workspace_bytes(int batch, int heads, int head_dim, int max_kv_len);
 int spatten_attn_decode_pq_local_v(const spatten_pq_local_v_args_t* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Quantised query: the decode step over the planes with integer dot products (opt-in; parity unpinned — the RTL multiplies
+ * fixed point by fixed point, DotProduct.scala, and the traces carry the width as quant_query_bit).  spatten_attn_decode_pq with
+ * ONE difference: the rotated query is quantised once per head and every key is scored as an exact integer times two scales.
+ *
+ * Query.  qr = the rotated query of head (b, h), each element already a model-dtype value (rotated exactly as
+ *   spatten_attn_decode_pq rotates it).  amax = max_i |qr_i| over the head's d elements, Q = 2^(query_bits-1) - 1,
+ *   q_scale = amax / Q (fp32, one rounding), q_int_i = clamp(rint(qr_i / q_scale), -Q, Q) — a nearest rounding of the true
+ *   quotient (which way a tie goes is unspecified).  An all-zero query gives q_scale = 0 and q_int = 0.
+ *   The call writes q_int (int8 [B,H,d], ELEMENT order, strides qi_sb / qi_sh in bytes = elements) and q_scale (fp32 [B,H],
+ *   contiguous) once per LAUNCHED head (rows of pruned heads stay untouched), from split 0 of the MSB pass, as vector stores.
+ * MSB pass.  A1_j = sum_i q_int_i msb_ij as int32 (|A1| <= 127 * 128 * 128 < 2^24: the conversion to fp32 is exact; the
+ *   offset-binary + 2^(kb-1) of the stored fields leaves exactly — an XOR of the sign bits at 8 bits, - 8 sum_i q_int_i at 4).
+ *   cq = q_scale * (16 / sqrt(d)) in fp32 (16 / sqrt(d) itself an fp32 constant: sqrt, reciprocal, exact scaling by 16);
+ *   s1_j = float(A1_j) * (key_scale_j * cq).  s1_j goes to msb_logit and, rounded to the model dtype, to the stash;
+ *   need_lsb = (1 / l_total) < threshold over the head's whole row, as in spatten_attn_decode_pq.
+ * Refetch pass (flagged heads).  A2_j = sum_i q_int_i lsb_ij (exact); s2_j = s1_j + float(A2_j) * (key_scale_j * (cq / 16)),
+ *   s1_j read from msb_logit (the MSB plane is not re-read; cq / 16 is exact).
+ *   fp32 roundings of a final logit: 16 / sqrt(d) (2), cq, key_scale * cq, the product; the LSB term's product; the add — at
+ *   most 8 per term: |s - s_exact| <= 8 * 2^-24 * (|s1| + |s2 - s1|), s_exact evaluated with q_int * q_scale as the query.
+ * Everything else — softmax, P.V over the quantised V plane, lse, head_abs_acc, split-N layout and merge, head_ids, both length
+ *   forms (kv_len / step_state), the compact refetch grid, SPATTEN_PQ_MSB_PASS_ONLY — is spatten_attn_decode_pq's.
+ *
+ * SPATTEN_ERR_INVALID: NULL q_int / q_scale, query_bits outside [4, 8], a wrong struct_size, q_int / qi_sb / qi_sh not
+ *   multiples of 8 (a lane exports 8 elements per store), and whatever spatten_attn_decode_pq refuses as invalid.
+ * SPATTEN_ERR_UNSUPPORTED (spatten_pq_qint_supported is the host rule, no GPU needed):
+ *   profile (6, 6)         a 6-bit field straddles bytes: no byte-wise integer dot without re-packing the piece
+ *   fp32 model dtype       the 16-bit dtypes are the deployed ones; the fp32 instantiations of both passes would double the count
+ *   step.k_new set         the in-launch append scores the new row from registers in its own instantiation: append with
+ *                          spatten_kv_append_planes first
+ *   the scores-only form   (the composed local-V step): spatten_attn_decode_pq_local_v has no quantised-query variant
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct spatten_pq_qint_args {
+  uint32_t struct_size; int32_t query_bits;      /* sizeof(spatten_pq_qint_args_t) of the caller; 4..8 */
+  spatten_pq_decode_args_t step;                 /* exactly as spatten_attn_decode_pq takes it */
+  int8_t* q_int;  int64_t qi_sb, qi_sh;          /* out, required: [B,H,d] */
+  float*  q_scale;                               /* out, required: [B,H] */
+} spatten_pq_qint_args_t;
+int spatten_attn_decode_pq_qint(const spatten_pq_qint_args_t* args, void* stream);
+/* 1 when spatten_attn_decode_pq_qint takes this geometry: dtype f16 / bf16, head_dim 64 / 128, profile (8, 8) or (4, 8),
+ * query_bits in [4, 8]; else 0. */
+int spatten_pq_qint_supported(int dtype, int head_dim, int key_msb_bits, int value_bits, int query_bits);
+
 /* Prefill over the planes (BASELINE.json configs[3]: prefill + progressive quantisation).  Same query / value / output /
  * mask / position arguments as spatten_attn_prefill; the keys come from the MSB / LSB planes: pass 1 scores every query
  * row from the MSB plane (logits in fp32), need_lsb[b,h,i] = (max_j prob_ij < threshold) per QUERY ROW (int32 [B,H,q_len],

@@ -116,6 +116,17 @@ class PQLocalVArgs(ctypes.Structure):
         ("workspace", c_void_p),
     ]
 
+
+class PQQintArgs(ctypes.Structure):
+    """``spatten_pq_qint_args_t`` (include/spatten.h): the profiled step with a quantised query (integer dot products)."""
+    _fields_ = [
+        ("struct_size", c_uint32), ("query_bits", c_int32),
+        ("step", PQDecodeArgs),
+        ("q_int", c_void_p), ("qi_sb", c_int64), ("qi_sh", c_int64),
+        ("q_scale", c_void_p),
+    ]
+
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libspatten_hip.so")
 if os.environ.get("SPATTEN_LIB"):          # developer A/B: a variant build of the library (tools/mb/build_variant.sh)
@@ -206,6 +217,10 @@ def _declare(lib):
     lib.spatten_pq_local_v_workspace_bytes.argtypes = [i, i, i, i]
     lib.spatten_attn_decode_pq_local_v.restype = c_int
     lib.spatten_attn_decode_pq_local_v.argtypes = [POINTER(PQLocalVArgs), p]
+    lib.spatten_attn_decode_pq_qint.restype = c_int
+    lib.spatten_attn_decode_pq_qint.argtypes = [POINTER(PQQintArgs), p]
+    lib.spatten_pq_qint_supported.restype = c_int
+    lib.spatten_pq_qint_supported.argtypes = [i, i, i, i, i]
     lib.spatten_prefill_workspace_bytes.restype = c_size_t
     lib.spatten_prefill_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
     lib.spatten_attn_prefill.restype = c_int

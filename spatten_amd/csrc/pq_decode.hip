@@ -59,6 +59,9 @@ struct PqvParams {
   // step's probabilities into acc[h, j] (j < prev_len; DYN: state word 3) from the fp32 logits that step left in msb_logit and its
   // (max, sum) in prev_lse — read before this pass overwrites the row, by the thread that overwrites it
   float* acc; int64_t acc_sh; const float* prev_lse; int prev_len;
+  // the QUANTISED QUERY form (QI, spatten_attn_decode_pq_qint): the rotated query quantised once per head to qmax = 2^(query_bits-1) - 1
+  // levels, every key scored with integer dot products; split 0 of the MSB pass exports q_int [B,H,d] (element order) and q_scale [B,H]
+  int8_t* qi_out; int64_t qi_sb, qi_sh; float* qs_out; int qmax;
 };
 
 // row-groups per pipelined tile.  r04 A/B at 8192 rows x 32 heads, profile (4, 8), MSB pass: 12: 20.0 us, 8: 16.6, 6: 16.4, 4: 14.8
@@ -177,13 +180,55 @@ __device__ inline void fma_piece(float (&o)[16], const uint32_t (&w)[W], float w
   for (int t = 0; t < 16; ++t) o[t] = fmaf(wgt, field_f32<BITS, W>(w, t), o[t]);
 }
 
+// ---- the quantised-query form (include/spatten.h "Quantised query"): integer group sum and the piece's integer dot ----------
+template <int CTRL> __device__ inline int dpp_mov_i(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true); }
+template <int WIDTH> __device__ inline int group_sum_i(int v) {
+  static_assert(WIDTH == 4 || WIDTH == 8, "group width");
+  v += dpp_mov_i<kDppXor1>(v);
+  v += dpp_mov_i<kDppXor2>(v);
+  if (WIDTH == 8) v += dpp_mov_i<kDppHalfMirror>(v);
+  return v;
+}
+__device__ inline uint32_t pack_i8x4(int a, int b, int c, int d) {
+  return (uint32_t)(a & 255) | ((uint32_t)(b & 255) << 8) | ((uint32_t)(c & 255) << 16) | ((uint32_t)(d & 255) << 24);
+}
+// The lane's 16 quantised query elements packed against the piece's dwords.  8-bit fields (byte t of the piece = field t): qp[j] =
+// elements 4j .. 4j + 3.  Nibble fields (nibble t at bit 4t; w & 0x0F0F0F0F = the even fields of a dword as bytes, (w >> 4) &
+// 0x0F0F0F0F the odd ones): qp[2j] = the even, qp[2j + 1] = the odd elements of dword j.
+template <int KBITS> __device__ inline void qint_pack(const int (&qi)[16], uint32_t (&qp)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (KBITS == 8) qp[j] = pack_i8x4(qi[4 * j], qi[4 * j + 1], qi[4 * j + 2], qi[4 * j + 3]);
+    else qp[j] = pack_i8x4(qi[8 * (j / 2) + (j & 1)], qi[8 * (j / 2) + (j & 1) + 2], qi[8 * (j / 2) + (j & 1) + 4], qi[8 * (j / 2) + (j & 1) + 6]);
+  }
+}
+// sum_t q_t field_t over the lane's piece + `init` (v_dot4c_i32_i8, exact).  8-bit fields hold msb + 128: the XOR of the sign bits
+// turns a byte into msb itself (two's complement).  Nibble fields are in [0, 15], positive as signed bytes: the MSB plane's + 8
+// leaves through init = -8 sum_t q_t, the LSB plane has none.
+template <int KBITS, int W> __device__ inline int qint_dot(const uint32_t (&w)[W], const uint32_t (&qp)[4], int init) {
+  int a = init;
+  if constexpr (KBITS == 8) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a = __builtin_amdgcn_sdot4((int)qp[j], (int)(w[j] ^ 0x80808080u), a, false);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      a = __builtin_amdgcn_sdot4((int)qp[2 * j], (int)(w[j] & 0x0F0F0F0Fu), a, false);
+      a = __builtin_amdgcn_sdot4((int)qp[2 * j + 1], (int)((w[j] >> 4) & 0x0F0F0F0Fu), a, false);
+    }
+  }
+  return a;
+}
+
 // APP (round 5): the MSB pass that also appends the step's row — its own instantiation: carried as a run-time branch the path cost every
 // OTHER caller 0.8-1.0 us per pass (a branch around the new token's loads behind the first tile breaks the exact vmcnt the
 // pipelined tiles rely on: same-call A/B, (4,8) 15.5 vs 14.65 us).
 // SO (scores only): no V traffic and no output — the stash, the fp32 logits (msb_logit: pass 1 all heads, the refetch pass
 // rewrites the flagged heads' rows with their final logits), lse and need_lsb; the kept-row select and the gather follow
-template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false>
+// QI: the quantised-query form — only the prologue (quantise, pack, export) and the per-row logit differ
+template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false, bool QI = false>
 __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams<T> p_in) {
+  static_assert(!QI || (sizeof(T) < 4 && KB != 6 && !APP && !SO), "the quantised-query form: 16-bit dtypes, (8, 8) / (4, 8), no append, full P.V");
   PqvParams<T> p = p_in;                         // (the compact refetch pass picks its split layout by the number of flagged heads)
   constexpr int LPR = D / 16;                    // lanes per row: lane c owns the row's piece c (16 elements)
   constexpr int RPI = kPqvThreads / LPR;         // rows per row-group
@@ -335,6 +380,49 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
     }
   }
   const float rsqrt_d = 1.0f / p.sqrt_d;
+  // ---- QI: amax over the head (every row-group holds the same query: the group max IS the head's), q_scale = amax / qmax,
+  // q_int = clamp(rint(qr / q_scale)) with the quotient's last-bit error taken out through the exact residual (so the result is a
+  // nearest rounding of the TRUE quotient), packed against the piece's dwords; split 0's first row-group exports both — buffer
+  // stores whose descriptor is empty for every other workgroup and whose offset is out of range for every other lane: no branch
+  uint32_t qp[4] = {0u, 0u, 0u, 0u};
+  int qbias = 0;
+  float cq = 0.f;
+  if constexpr (QI) {
+    float amax = 0.f;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) amax = fmaxf(amax, fabsf(qv[t]));
+    amax = fmaxf(amax, dpp_mov<kDppXor1>(amax));
+    amax = fmaxf(amax, dpp_mov<kDppXor2>(amax));
+    if (LPR == 8) amax = fmaxf(amax, dpp_mov<kDppHalfMirror>(amax));
+    const float qmaxf = (float)p.qmax;
+    const float qs = amax / qmaxf;
+    const float qs_div = qs > 0.f ? qs : 1.0f;       // (an all-zero query: q_scale = 0, q_int = 0)
+    int qi[16];
+    int qsum_i = 0;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+      float rq = rintf(qv[t] / qs_div);
+      const float e = fmaf(-rq, qs_div, qv[t]);      // qr - rq q_scale, one rounding
+      rq += (e > 0.5f * qs_div) ? 1.f : (e < -0.5f * qs_div) ? -1.f : 0.f;
+      qi[t] = (int)fminf(fmaxf(rq, -qmaxf), qmaxf);
+      qsum_i += qi[t];
+    }
+    qint_pack<KBITS>(qi, qp);
+    qbias = (PASS == 1 && KBITS == 4) ? -8 * qsum_i : 0;
+    cq = qs * (16.f * rsqrt_d);
+    if constexpr (PASS == 1) {
+      const bool exporter = blockIdx.x == 0;                            // (wave-uniform; pass 1 is never compacted)
+      const __amdgpu_buffer_rsrc_t rs_qi = make_rsrc(p.qi_out + b * p.qi_sb + h * p.qi_sh, exporter ? D : 0);
+      const __amdgpu_buffer_rsrc_t rs_qs = make_rsrc(p.qs_out + unit, exporter ? 4 : 0);
+      const uint32_t wlo[2] = {pack_i8x4(qi[0], qi[1], qi[2], qi[3]), pack_i8x4(qi[4], qi[5], qi[6], qi[7])};
+      const uint32_t whi[2] = {pack_i8x4(qi[8], qi[9], qi[10], qi[11]), pack_i8x4(qi[12], qi[13], qi[14], qi[15])};
+      const int vo_q = (r == 0) ? 8 * c : 0x40000000;
+      bstore<2>(rs_qi, vo_q, 0, wlo);                                   // elements 8c .. 8c + 7
+      bstore<2>(rs_qi, vo_q, HALF, whi);                                // elements d/2 + 8c ..
+      const uint32_t wq[1] = {__float_as_uint(qs)};
+      bstore<1>(rs_qs, tid == 0 ? 0 : 0x40000000, 0, wq);
+    }
+  }
   // stash / MSB-logit stores without branches: buffer stores whose descriptor ends at row `hi` (a row past it is dropped by
   // the bounds check) and whose per-lane offset is out of range for every lane but the row's first (c != 0)
   T* stashp = p.scores ? p.scores + b * p.sc_sb + h * p.sc_sh : nullptr;
@@ -398,6 +486,12 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
 #pragma unroll
     for (int u = 0; u < UP; ++u) {
       float a;
+      if constexpr (QI) {    // A = sum_i q_int_i field_i as int32 (|A| < 2^24: the conversion is exact); s = float(A) (key_scale cq)
+        const int ai = group_sum_i<LPR>(qint_dot<KBITS, KW>(tl.kw[u], qp, qbias));
+        const float s = (float)ai * (__uint_as_float(tl.ks[u]) * (PASS == 1 ? cq : cq * 0.0625f));
+        sc[u] = (PASS == 2) ? __uint_as_float(tl.lg[u]) + s : s;
+        continue;
+      }
       if (KBITS == 4) {      // fields hold msb + 8 (pass 1) / the LSB nibble (pass 2)
         a = NibbleDot<T>::dot(qn[0], tl.kw[u][0], PASS == 1 ? 8.f : 0.f) + NibbleDot<T>::dot(qn[1], tl.kw[u][KW - 1], PASS == 1 ? 8.f : 0.f);
       } else {               // fields hold msb + 2^(KB-1)
@@ -663,16 +757,17 @@ template <typename K> static int resident_capacity(K kernel) {
   return std::max(1, std::min(per_cu, 2)) * cus;
 }
 
-template <typename T, int D, int KB, int VB, bool SO = false>
+template <typename T, int D, int KB, int VB, bool SO = false, bool QI = false>
 static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st) {
   const bool app = p.k_new != nullptr;
   constexpr int UP = kPqvUp;
   const dim3 grid((unsigned)p.S, (unsigned)n_active, (unsigned)p.B), blk(kPqvThreads);
   // (the pass-1 and pass-2 kernels of a profile have different register footprints: the smaller capacity decides)
-  static const int cap_static = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, false, UP>),
-                                         resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, false, UP>));
-  static const int cap_dyn = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP>),
-                                      resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP>));
+  // (QI: its own kernels' answer; their register footprint is not the fp32-query kernels')
+  static const int cap_static = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, QI>),
+                                         resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, QI>));
+  static const int cap_dyn = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, QI>),
+                                      resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, QI>));
   p.poll_merge = (p.S > 1 && (long long)p.S * n_active * p.B <= (dyn ? cap_dyn : cap_static)) ? 1 : 0;
   // ---- the refetch pass (round 6): at the reference traces' rate 2-3 of 30 heads are flagged per layer-step; laid out like pass 1
   // their rows sit on S CUs each and the pass takes as long as if every head were flagged (a CU streams at ~21 B/ns).  So pass 2
@@ -691,6 +786,16 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
   }
   const dim3 grid2((unsigned)p2.S, (unsigned)n_active, (unsigned)p.B);
   // (SO: the scores-only kernels need no more registers than the full ones — the capacities above stay a safe bound)
+  if constexpr (QI) {      // (no append and no scores-only form: spatten_attn_decode_pq_qint refuses them)
+    if (dyn) {
+      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, true>), grid2, blk, 0, st, p2);
+    } else {
+      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, true>), grid2, blk, 0, st, p2);
+    }
+    return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
+  } else
   if (dyn) {
     if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, true, SO>), grid, blk, 0, st, p);
     else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, SO>), grid, blk, 0, st, p);
@@ -705,9 +810,12 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
 
 // the local-V extras of spatten_attn_decode_pq_local_v (NULL: the plain profiled step)
 struct PqLvExtra { float* acc; int64_t acc_sh; const float* prev_lse; int prev_len; };
+// the quantised-query extras of spatten_attn_decode_pq_qint (NULL: the query stays in the model dtype)
+struct PqQintExtra { int8_t* q_int; int64_t qi_sb, qi_sh; float* q_scale; int qmax; };
 
 template <typename T>
-static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st, const PqLvExtra* lv = nullptr) {
+static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st, const PqLvExtra* lv = nullptr,
+                   const PqQintExtra* qx = nullptr) {
   const int kb = a->planes->key_msb_bits;      // (the value width follows: supported profiles are (4, 8), (8, 8), (6, 6))
   const int d = a->head_dim;
   const int n_active = a->head_ids ? a->n_active_heads : a->heads;
@@ -748,10 +856,17 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
   p.nr_row = a->step_state ? 1 : std::min(a->kv_len - 1, a->table_rows - 1);
   p.acc = lv ? lv->acc : nullptr; p.acc_sh = lv ? lv->acc_sh : 0;
   p.prev_lse = (lv && lv->acc) ? lv->prev_lse : a->lse; p.prev_len = (lv && lv->acc) ? lv->prev_len : 0;
+  p.qi_out = qx ? qx->q_int : nullptr; p.qi_sb = qx ? qx->qi_sb : 0; p.qi_sh = qx ? qx->qi_sh : 0;
+  p.qs_out = qx ? qx->q_scale : nullptr; p.qmax = qx ? qx->qmax : 0;
   const bool dyn = a->step_state != nullptr, msb_only = (a->flags & SPATTEN_PQ_MSB_PASS_ONLY) != 0;
 #define SPATTEN_PQV(DD, KB, VB)                                                                     \
-  return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, st)            \
-            : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, st)
+  do {                                                                                              \
+    if constexpr (sizeof(T) < 4 && KB != 6) {                                                       \
+      if (qx) return launch_pqv<T, DD, KB, VB, false, true>(p, n_active, dyn, msb_only, st);        \
+    }                                                                                               \
+    return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, st)                     \
+              : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, st);                          \
+  } while (0)
   if (d == 128) {
     if (kb == 4) SPATTEN_PQV(128, 4, 8);
     if (kb == 8) SPATTEN_PQV(128, 8, 8);
@@ -975,6 +1090,30 @@ extern "C" int spatten_attn_decode_pq(const spatten_pq_decode_args_t* a, void* s
   if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream);
   if (a->dtype == SPATTEN_F16) return run_pqv<f16_t>(a, pd, (hipStream_t)stream);
   return run_pqv<float>(a, pd, (hipStream_t)stream);
+}
+
+extern "C" int spatten_pq_qint_supported(int dtype, int head_dim, int key_msb_bits, int value_bits, int query_bits) {
+  if (dtype != SPATTEN_BF16 && dtype != SPATTEN_F16) return 0;
+  if (head_dim != 64 && head_dim != 128) return 0;
+  if (!((key_msb_bits == 8 || key_msb_bits == 4) && value_bits == 8)) return 0;
+  return query_bits >= 4 && query_bits <= 8;
+}
+
+extern "C" int spatten_attn_decode_pq_qint(const spatten_pq_qint_args_t* qa, void* stream) {
+  if (!qa || qa->struct_size != sizeof(spatten_pq_qint_args_t)) return SPATTEN_ERR_INVALID;
+  if (!qa->q_int || !qa->q_scale || qa->query_bits < 4 || qa->query_bits > 8) return SPATTEN_ERR_INVALID;
+  const spatten_pq_decode_args_t* a = &qa->step;
+  PlanesDev pd;
+  const int rc = pq_validate(a, pd);
+  if (rc != SPATTEN_OK) return rc;
+  // (the exported query leaves as two 8-byte stores per lane)
+  if (((uintptr_t)qa->q_int | (uintptr_t)qa->qi_sb | (uintptr_t)qa->qi_sh) & 7u) return SPATTEN_ERR_INVALID;
+  if (a->k_new != nullptr) return SPATTEN_ERR_UNSUPPORTED;
+  if (!spatten_pq_qint_supported(a->dtype, a->head_dim, a->planes->key_msb_bits, a->planes->value_bits, qa->query_bits))
+    return SPATTEN_ERR_UNSUPPORTED;
+  PqQintExtra qx{qa->q_int, qa->qi_sb, qa->qi_sh, qa->q_scale, (1 << (qa->query_bits - 1)) - 1};
+  if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream, nullptr, &qx);
+  return run_pqv<f16_t>(a, pd, (hipStream_t)stream, nullptr, &qx);
 }
 
 extern "C" size_t spatten_pq_local_v_workspace_bytes(int batch, int heads, int head_dim, int max_kv_len) {

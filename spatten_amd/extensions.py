@@ -23,6 +23,9 @@ against those restatements.
                                 With a profile the refetch pass reads ONLY the LSB plane (+ the stashed MSB logits).
     local_v_keep=f              local V pruning at decode (SpAttenController.scala:546-558,591-612): only the
                                 ceil(f * kv_len) most probable keys of a head fetch their V row.
+    pq_query_bits=n             with pq_profile (8, 8) / (4, 8): the rotated query quantised to n bits (4..8) once per head and the
+                                keys scored with integer dot products (spatten_attn_decode_pq_qint; DotProduct.scala, the traces'
+                                quant_query_bit); the step's row is appended by spatten_kv_append_planes first
     pq_profile + local_v_keep   the whole cascade of the RTL in one decode step (spatten_attn_decode_pq_local_v): MSB scores,
                                 LSB refetch for the flagged heads, V fetched only for the kept keys and only from the quantised
                                 V plane, with or without importance_mode="cascade" (fused, deferred by one step as above) and
@@ -63,6 +66,7 @@ class LayerState:
         self.need_lsb: Optional[torch.Tensor] = None                # int32 [B*H]
         self.out: Optional[torch.Tensor] = None                     # [B, H*d], zero in the pruned heads' slices
         self.pq_planes = None           # the profiled local-V step: the planes whose msb_logit holds the last step's logits
+        self.q_quant = None             # pq_query_bits: (q_int int8 [B,H,d], q_scale fp32 [B,H]) of the last step (fixed addresses)
 
     def ensure(self, B, H, d, n, dtype, device, want_acc):
         cap = kv_slab.round_capacity(n + kv_slab.GROW)
@@ -88,6 +92,12 @@ class LayerState:
         if self.out is None or self.out.shape != (B, H * d) or self.out.dtype != dtype:
             self.out = torch.zeros(B, H * d, dtype=dtype, device=device)
 
+    def ensure_q_quant(self, B, H, d, device):
+        if self.q_quant is None or self.q_quant[0].shape != (B, H, d):
+            self.q_quant = (torch.zeros(B, H, d, dtype=torch.int8, device=device),
+                            torch.zeros(B, H, dtype=torch.float32, device=device))
+        return self.q_quant
+
 
 def _per_layer(x, n_layers: int, name: str):
     if x is None:
@@ -104,7 +114,17 @@ class SpattenExtensions:
     def __init__(self, cache, n_layers: int, cascade: bool = False,
                  head_keep: Union[None, int, Sequence[int]] = None, pq_threshold: Optional[float] = None,
                  local_v_keep: Optional[float] = None, layer_keep: Optional[Sequence[int]] = None, head_parallel=None,
-                 pq_profile: Optional[Sequence[int]] = None):
+                 pq_profile: Optional[Sequence[int]] = None, pq_query_bits: Optional[int] = None):
+        if pq_query_bits is not None:
+            if pq_profile is None or tuple(int(x) for x in pq_profile) not in ((8, 8), (4, 8)):
+                raise ValueError("pq_query_bits needs pq_profile (8, 8) or (4, 8) (the integer-dot decode has no (6, 6) form)")
+            if local_v_keep is not None:
+                raise ValueError("pq_query_bits cannot be combined with local_v_keep (the composed local-V step has no "
+                                 "quantised-query form)")
+            if int(pq_query_bits) != pq_query_bits or not 4 <= int(pq_query_bits) <= 8:
+                raise ValueError("pq_query_bits is an integer in [4, 8]")
+            pq_query_bits = int(pq_query_bits)
+        self.pq_query_bits = pq_query_bits
         if pq_profile is not None:
             pq_profile = (int(pq_profile[0]), int(pq_profile[1]))
             if pq_threshold is None:
@@ -217,7 +237,8 @@ class SpattenExtensions:
             slab.ensure_pq(kv_len - 1, self.pq_profile, H)
             if slab.pq.capacity < cap:
                 raise RuntimeError("progressive-quant planes smaller than the slab capacity")
-            if st.head_ids is None:      # (r05) every head is launched: the append + plane rows ride inside the MSB pass
+            qb = self.pq_query_bits      # (the quantised-query launch appends nothing: the head list's route)
+            if st.head_ids is None and qb is None:      # (r05) every head is launched: the append + plane rows ride inside the MSB pass
                 app = (k_new, v_new, slab.k, slab.kr, slab.v)
             else:                        # a head list: the pruned heads' rows are still appended (a later turn may re-rank the heads)
                 ops.kv_append_planes(k_new, v_new, slab.k, slab.kr, slab.v, slab.pq, 0, cos, sin, step=step)
@@ -225,7 +246,8 @@ class SpattenExtensions:
             slab.pq_len = kv_len
             ops.attn_decode_pqv(q, slab.pq, cap, cos, sin, 0, self.pq_threshold, out=st.out, need_lsb=st.need_lsb,
                                 scores=st.stash[0], lse=st.lse[0], head_ids=st.head_ids,
-                                head_abs=st.head_abs if self.head_keep is not None else None, step=step, append=app)
+                                head_abs=st.head_abs if self.head_keep is not None else None, step=step, append=app,
+                                query_bits=qb, q_quant=None if qb is None else st.ensure_q_quant(B, H, d, q.device))
             return st.out, st.stash[0][:, :, None, :kv_len]
         if self.pq_threshold is not None:
             # rows [0, kv_len - 1) packed with host lengths BEFORE the capture (the eager first step of the binding does it:
@@ -279,14 +301,16 @@ class SpattenExtensions:
         head_abs = st.head_abs if self.head_keep is not None else None
         if self.pq_threshold is not None and self.pq_profile is not None:
             slab.ensure_pq(past_len, self.pq_profile, H)                  # (rows a prefill left unpacked, if any)
-            if st.head_ids is None:
+            qb = self.pq_query_bits
+            if st.head_ids is None and qb is None:
                 app = (k_new, v_new, slab.k, slab.kr, slab.v)
             else:
                 ops.kv_append_planes(k_new, v_new, slab.k, slab.kr, slab.v, slab.pq, past_len, cos, sin)
                 app = None
             slab.pq_len = kv_len
             ops.attn_decode_pqv(q, slab.pq, kv_len, cos, sin, past_len, self.pq_threshold, out=st.out, need_lsb=st.need_lsb,
-                                scores=stash, lse=lse, head_ids=st.head_ids, head_abs=head_abs, layout=slab.capacity, append=app)
+                                scores=stash, lse=lse, head_ids=st.head_ids, head_abs=head_abs, layout=slab.capacity, append=app,
+                                query_bits=qb, q_quant=None if qb is None else st.ensure_q_quant(B, H, d, q.device))
         elif self.pq_threshold is not None:
             ops.kv_append(k_new[:, :, None], v_new[:, :, None], slab.k, slab.kr, slab.v, past_len, cos, sin)
             slab.ensure_pq(kv_len)

@@ -1428,11 +1428,26 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
                     scores: Optional[torch.Tensor] = None, lse: Optional[torch.Tensor] = None,
                     head_ids: Optional[torch.Tensor] = None, head_abs: Optional[torch.Tensor] = None,
                     step: Optional["StepState"] = None, layout: int = 0, n_splits: int = 0, msb_only: bool = False,
-                    workspace: Optional[DecodeWorkspace] = None, append=None) -> torch.Tensor:
+                    workspace: Optional[DecodeWorkspace] = None, append=None, query_bits: Optional[int] = None,
+                    q_quant: Optional[tuple] = None) -> torch.Tensor:
     """Decode over the profiled planes (spatten_attn_decode_pq): MSB pass + LSB-only refetch for the flagged heads, P.V over
     the quantised values.  q [B,H,d]; returns out [B, H*d]; ``need_lsb`` int32 [B*H] is written.
     ``append`` = (k_new, v_new, k_cache | None, kr_cache, v_cache): the step's append INSIDE the MSB pass (round 5) — row kv_len - 1
-    of the cache planes and of every quantised plane, for the launched heads (what ``kv_append_planes`` leaves)."""
+    of the cache planes and of every quantised plane, for the launched heads (what ``kv_append_planes`` leaves).
+    ``query_bits`` (4..8; None: the query stays in the model dtype): the quantised-query form (spatten_attn_decode_pq_qint) —
+    the rotated query quantised once per head, every key scored with integer dot products.  ``q_quant`` = (q_int int8 [B,H,d],
+    q_scale fp32 [B,H]) receives the quantised query of the launched heads (allocated when absent).  f16 / bf16, profiles (8, 8)
+    and (4, 8); no ``append`` (call ``kv_append_planes`` first)."""
+    if query_bits is not None:
+        if append is not None:
+            raise NotImplementedError("attn_decode_pqv(query_bits=...) does not append inside the launch: call "
+                                      "ops.kv_append_planes(...) first and pass append=None")
+        if int(query_bits) != query_bits or not 4 <= int(query_bits) <= 8:
+            raise ValueError(f"query_bits {query_bits!r}: an integer in [4, 8]")
+        if not pq_qint_supported(q.dtype, q.shape[2], planes.key_bits, planes.value_bits, int(query_bits)):
+            raise NotImplementedError(f"attn_decode_pqv(query_bits=...): {q.dtype}, head_dim {q.shape[2]}, profile "
+                                      f"{(planes.key_bits, planes.value_bits)} has no quantised-query kernel (f16 / bf16, head_dim "
+                                      "64 / 128, profiles (8, 8) and (4, 8))")
     _dev(q, planes.msb, cos, sin, out, need_lsb, scores, lse, head_ids, head_abs)
     B, H, d = q.shape
     Hkv = planes.msb.shape[1]
@@ -1481,8 +1496,32 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
         a.k_new, a.v_new, a.new_sb, a.new_sh = k_new.data_ptr(), v_new.data_ptr(), k_new.stride(0), k_new.stride(1)
         a.k_cache, a.kr_cache, a.v_cache = _ptr(k_cache), kr_cache.data_ptr(), v_cache.data_ptr()
         a.kv_sb, a.kv_sh = kr_cache.stride(0), kr_cache.stride(1)
+    if query_bits is not None:
+        if q_quant is None:
+            q_quant = (torch.zeros(B, H, d, dtype=torch.int8, device=q.device), torch.zeros(B, H, dtype=torch.float32, device=q.device))
+        q_int, q_scale = q_quant
+        _dev(q_int, q_scale)
+        if q_int.dtype != torch.int8 or q_int.shape != (B, H, d) or q_int.stride(2) != 1 or q_scale.dtype != torch.float32 \
+                or q_scale.shape != (B, H) or not q_scale.is_contiguous():
+            raise ValueError("q_quant = (q_int int8 [B,H,d] with contiguous rows, q_scale fp32 [B,H] contiguous)")
+        qa = _lib.PQQintArgs()
+        qa.struct_size, qa.query_bits = ctypes.sizeof(_lib.PQQintArgs), int(query_bits)
+        qa.step = a
+        qa.q_int, qa.qi_sb, qa.qi_sh = q_int.data_ptr(), q_int.stride(0), q_int.stride(1)
+        qa.q_scale = q_scale.data_ptr()
+        _lib.check(_lib.load().spatten_attn_decode_pq_qint(ctypes.byref(qa), stream), "spatten_attn_decode_pq_qint")
+        return out
     _lib.check(_lib.load().spatten_attn_decode_pq(ctypes.byref(a), stream), "spatten_attn_decode_pq")
     return out
+
+
+def pq_qint_supported(dtype: torch.dtype, head_dim: int, key_bits: int, value_bits: int, query_bits: int) -> bool:
+    """Whether ``attn_decode_pqv(..., query_bits=)`` takes this geometry (spatten_pq_qint_supported: host rule, no GPU): f16 / bf16,
+    head_dim 64 / 128, profile (8, 8) or (4, 8), query_bits in [4, 8]."""
+    code = _DT.get(dtype)
+    if code is None:
+        return False
+    return bool(_lib.load().spatten_pq_qint_supported(code, int(head_dim), int(key_bits), int(value_bits), int(query_bits)))
 
 
 _pqlv_ws_cache = _LRU(8)

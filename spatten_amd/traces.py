@@ -12,6 +12,8 @@ per-layer keep ratios that ``run_spatten_synthetic.py --trace`` applies to a mod
 ``CascadeSchedule.pq_profile()`` the bit profile (key MSB bits, value bits) the accelerator model runs the trace at —
 the mapping of the reference's harness (TestSpAtten.scala:64-97): ``quant_key_bit`` -1 / 10 / 12 -> 8 with the requant
 forced on, ``quant_value_bit`` -1 / 10 / 12 -> 8; 6 is the fused (6, 2) fetch profile (TestSpAtten.scala:173-176);
+``CascadeSchedule.query_bits()`` maps ``quant_query_bit`` the same way: above 8 or -1 -> None (the query stays in the model
+dtype), 4..8 -> the width of the quantised-query decode (``pq_query_bits``).
 ``auto_requant_incre`` = the LSB bits added by a refetch (4 in every trace, the RTL's requantBitCount,
 SpAttenController.scala:35).  ``if_rescale_previous_importance`` is carried as a field; NO code of the reference reads it
 (it is not among the columns TestSpAtten.scala maps, and the Python plugin has no accumulated importance at all), so there
@@ -43,6 +45,7 @@ class LayerStep:
     values: int = 0            # value_fetch_num (local V pruning)
     key_bits: int = -1         # quant_key_bit as written in the trace (-1: unquantised in the software model)
     value_bits: int = -1       # quant_value_bit
+    query_bits: int = -1       # quant_query_bit as written in the trace (16 in the reference's traces: the query is not quantised)
     lsb_bits: int = -1         # auto_requant_incre: bits a refetch adds
     rescale_previous_importance: bool = False
     requant: bool = False
@@ -81,6 +84,21 @@ class CascadeSchedule:
             best = (kb, vb) if best is None else (max(best[0], kb), max(best[1], vb))
         return best
 
+    def query_bits(self, iteration: int = 0):
+        """The query width the trace runs at, mapped as ``pq_profile()`` maps the key width: a ``quant_query_bit`` above 8 or of
+        -1 -> None (the 16-bit query: the model dtype, today's path); 4..8 -> that width, what ``enable_spatten_llm(...,
+        pq_query_bits=...)`` should be given.  The widest over the layers; a width below 4 is not one the integer-dot decode
+        takes (ValueError)."""
+        best = None
+        for s in self.layers(iteration):
+            qb = s.query_bits
+            if qb == -1 or qb > 8:
+                return None
+            if qb < 4:
+                raise ValueError(f"layer {s.layer}: quant_query_bit {qb} is below the 4 bits the quantised-query decode takes")
+            best = qb if best is None else max(best, qb)
+        return best
+
     def fractions(self, iteration: int = 0):
         """Per layer: (token keep ratio, local-V keep ratio, head keep ratio, requant threshold or None)."""
         steps = self.layers(iteration)
@@ -117,6 +135,7 @@ def read_trace(path: str) -> CascadeSchedule:
             st.keys = int(r["key_fetch_num"])
             st.values = int(r["value_fetch_num"])
             st.key_bits, st.value_bits = int(r["quant_key_bit"]), int(r["quant_value_bit"])
+            st.query_bits = int(r["quant_query_bit"])
             st.lsb_bits = int(r["auto_requant_incre"])
             st.rescale_previous_importance = st.rescale_previous_importance or _b(r["if_rescale_previous_importance"])
             st.requant = st.requant or _b(r["if_requant"])
