@@ -731,6 +731,46 @@ int spatten_attn_decode_pq_qint(const spatten_pq_qint_args_t* args, void* stream
  * query_bits in [4, 8]; else 0. */
 int spatten_pq_qint_supported(int dtype, int head_dim, int key_msb_bits, int value_bits, int query_bits);
 
+/* ------------------------------------------------------------------------------------------------
+ * Grouped quantised-query decode: spatten_attn_decode_pq_qint for a GROUPED-QUERY model (heads = G * kv_heads) with ONE plane
+ * stream per KV head (opt-in; parity unpinned as above).  spatten_attn_decode_pq_qint launches one workgroup column per query
+ * head: the G heads of a group each fetch their kv head's MSB, scale and value planes.  Here the MSB pass has one workgroup
+ * column per KV head (grid = (splits, kv_heads, batch)): a plane row is fetched once per group and scored for all G heads on
+ * the int8 matrix cores.  Same argument block, same results: q_int / q_scale, msb_logit, the stash, need_lsb, lse, out, the
+ * refetch pass for the flagged heads, SPATTEN_PQ_MSB_PASS_ONLY, both length forms (kv_len / step_state), the shared decode
+ * workspace with its split-N merge (launches of every decode kind may alternate on one workspace).
+ *
+ * Query.  Quantised by the routine spatten_attn_decode_pq_qint uses: q_int and q_scale are bit-identical to that call's.
+ * MSB pass.  S^T = Kmsb Qint^T with v_mfma_i32_32x32x32_i8: the group's G quantised queries are the first G columns of the B
+ *   operand (the rest zeros), the signed key operand is the stored byte XOR 0x80; the plane's piece order is kept and the query
+ *   operand permuted to match (an integer dot does not depend on the order of its terms).  A1 is the same exact integer and the
+ *   scale chain the same fp32 operations — cq = q_scale * (16 / sqrt(d)), s1 = float(A1) * (key_scale * cq) — so msb_logit and
+ *   the MSB-only stash are bit-identical to spatten_attn_decode_pq_qint's.
+ * P.V.  O^T = Vt W^T with v_mfma_f32_32x32x16_bf16 for BOTH model dtypes (an 8-bit qv is exact in bf16; f16 weights would
+ *   underflow).  The weight w_j = p_j * val_scale_j (fp32) enters as TWO bf16 values, hi = bf16(w), lo = bf16(w - hi): two
+ *   products with exact terms, fp32 sums.  (One bf16 weight alone costs 2^-9 relative per term: inside the output criterion in
+ *   bf16, 3.6 times outside it in f16.)  The sums run in another order than the per-head form's: out and lse agree with it to
+ *   rounding, not bit for bit.  need_lsb = (1 / l_total) < threshold per query head, as there.
+ * Refetch pass.  spatten_attn_decode_pq_qint's own compact pass (grid rows = the flagged QUERY heads) behind the grouped MSB
+ *   pass: a grouped refetch is not provided.
+ *
+ * SPATTEN_ERR_INVALID: as spatten_attn_decode_pq_qint.
+ * SPATTEN_ERR_UNSUPPORTED (spatten_pq_qint_gqa_supported is the host rule, no GPU needed):
+ *   heads == kv_heads, or G = heads / kv_heads > 32     nothing to group / a group is the 32 columns of one MFMA B operand
+ *   head_dim 64            the operand maps and the LDS ring are laid out for 128-byte plane rows
+ *   profile (4, 8), (6, 6) the int8 MFMA takes the 8-bit MSB plane as it lies; nibble and 6-bit fields would need unpacking
+ *   fp32 model dtype       as spatten_attn_decode_pq_qint
+ *   step.head_ids or step.head_abs_acc set      a workgroup column is a KV head and the head list is a device array: head
+ *                          pruning takes the per-head form
+ *   step.k_new set         as spatten_attn_decode_pq_qint: append with spatten_kv_append_planes first
+ *   kv_len >= 2^24         32-bit byte offsets inside a plane
+ * ---------------------------------------------------------------------------------------------- */
+int spatten_attn_decode_pq_qint_gqa(const spatten_pq_qint_args_t* args, void* stream);
+/* 1 when spatten_attn_decode_pq_qint_gqa takes this geometry: dtype f16 / bf16, heads % kv_heads == 0 with G = heads / kv_heads
+ * in [2, 32], head_dim 128, profile (8, 8), query_bits in [4, 8]; else 0. */
+int spatten_pq_qint_gqa_supported(int dtype, int heads, int kv_heads, int head_dim, int key_msb_bits, int value_bits,
+                                  int query_bits);
+
 /* Prefill over the planes (BASELINE.json configs[3]: prefill + progressive quantisation).  Same query / value / output /
  * mask / position arguments as spatten_attn_prefill; the keys come from the MSB / LSB planes: pass 1 scores every query
  * row from the MSB plane (logits in fp32), need_lsb[b,h,i] = (max_j prob_ij < threshold) per QUERY ROW (int32 [B,H,q_len],

@@ -221,6 +221,10 @@ def _declare(lib):
     lib.spatten_attn_decode_pq_qint.argtypes = [POINTER(PQQintArgs), p]
     lib.spatten_pq_qint_supported.restype = c_int
     lib.spatten_pq_qint_supported.argtypes = [i, i, i, i, i]
+    lib.spatten_attn_decode_pq_qint_gqa.restype = c_int
+    lib.spatten_attn_decode_pq_qint_gqa.argtypes = [POINTER(PQQintArgs), p]
+    lib.spatten_pq_qint_gqa_supported.restype = c_int
+    lib.spatten_pq_qint_gqa_supported.argtypes = [i, i, i, i, i, i, i]
     lib.spatten_prefill_workspace_bytes.restype = c_size_t
     lib.spatten_prefill_workspace_bytes.argtypes = [i, i, i, i, i, i, i]
     lib.spatten_attn_prefill.restype = c_int

@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "pq_pack.h"
+#include "pq_qint.h"
 #include "select_row.h"
 
 namespace spatten {
@@ -188,9 +189,6 @@ template <int WIDTH> __device__ inline int group_sum_i(int v) {
   v += dpp_mov_i<kDppXor2>(v);
   if (WIDTH == 8) v += dpp_mov_i<kDppHalfMirror>(v);
   return v;
-}
-__device__ inline uint32_t pack_i8x4(int a, int b, int c, int d) {
-  return (uint32_t)(a & 255) | ((uint32_t)(b & 255) << 8) | ((uint32_t)(c & 255) << 16) | ((uint32_t)(d & 255) << 24);
 }
 // The lane's 16 quantised query elements packed against the piece's dwords.  8-bit fields (byte t of the piece = field t): qp[j] =
 // elements 4j .. 4j + 3.  Nibble fields (nibble t at bit 4t; w & 0x0F0F0F0F = the even fields of a dword as bytes, (w >> 4) &
@@ -381,8 +379,8 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   }
   const float rsqrt_d = 1.0f / p.sqrt_d;
   // ---- QI: amax over the head (every row-group holds the same query: the group max IS the head's), q_scale = amax / qmax,
-  // q_int = clamp(rint(qr / q_scale)) with the quotient's last-bit error taken out through the exact residual (so the result is a
-  // nearest rounding of the TRUE quotient), packed against the piece's dwords; split 0's first row-group exports both — buffer
+  // q_int = the nearest rounding of qr / q_scale (pq_qint.h: the routine the grouped MSB pass shares), packed against the piece's
+  // dwords; split 0's first row-group exports both — buffer
   // stores whose descriptor is empty for every other workgroup and whose offset is out of range for every other lane: no branch
   uint32_t qp[4] = {0u, 0u, 0u, 0u};
   int qbias = 0;
@@ -395,16 +393,13 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
     amax = fmaxf(amax, dpp_mov<kDppXor2>(amax));
     if (LPR == 8) amax = fmaxf(amax, dpp_mov<kDppHalfMirror>(amax));
     const float qmaxf = (float)p.qmax;
-    const float qs = amax / qmaxf;
-    const float qs_div = qs > 0.f ? qs : 1.0f;       // (an all-zero query: q_scale = 0, q_int = 0)
+    float qs, qs_div;
+    qint_scale(amax, qmaxf, qs, qs_div);
     int qi[16];
     int qsum_i = 0;
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
-      float rq = rintf(qv[t] / qs_div);
-      const float e = fmaf(-rq, qs_div, qv[t]);      // qr - rq q_scale, one rounding
-      rq += (e > 0.5f * qs_div) ? 1.f : (e < -0.5f * qs_div) ? -1.f : 0.f;
-      qi[t] = (int)fminf(fmaxf(rq, -qmaxf), qmaxf);
+      qi[t] = qint_round(qv[t], qs_div, qmaxf);
       qsum_i += qi[t];
     }
     qint_pack<KBITS>(qi, qp);
@@ -758,7 +753,7 @@ template <typename K> static int resident_capacity(K kernel) {
 }
 
 template <typename T, int D, int KB, int VB, bool SO = false, bool QI = false>
-static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st) {
+static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st, bool refetch_only = false) {
   const bool app = p.k_new != nullptr;
   constexpr int UP = kPqvUp;
   const dim3 grid((unsigned)p.S, (unsigned)n_active, (unsigned)p.B), blk(kPqvThreads);
@@ -787,11 +782,12 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
   const dim3 grid2((unsigned)p2.S, (unsigned)n_active, (unsigned)p.B);
   // (SO: the scores-only kernels need no more registers than the full ones — the capacities above stay a safe bound)
   if constexpr (QI) {      // (no append and no scores-only form: spatten_attn_decode_pq_qint refuses them)
+    // (refetch_only: the grouped MSB pass of pq_gqa.hip has run in pass 1's place)
     if (dyn) {
-      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, true>), grid, blk, 0, st, p);
+      if (!refetch_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, true>), grid, blk, 0, st, p);
       if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, true>), grid2, blk, 0, st, p2);
     } else {
-      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, true>), grid, blk, 0, st, p);
+      if (!refetch_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, true>), grid, blk, 0, st, p);
       if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, true>), grid2, blk, 0, st, p2);
     }
     return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
@@ -810,12 +806,10 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
 
 // the local-V extras of spatten_attn_decode_pq_local_v (NULL: the plain profiled step)
 struct PqLvExtra { float* acc; int64_t acc_sh; const float* prev_lse; int prev_len; };
-// the quantised-query extras of spatten_attn_decode_pq_qint (NULL: the query stays in the model dtype)
-struct PqQintExtra { int8_t* q_int; int64_t qi_sb, qi_sh; float* q_scale; int qmax; };
 
 template <typename T>
 static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st, const PqLvExtra* lv = nullptr,
-                   const PqQintExtra* qx = nullptr) {
+                   const PqQintExtra* qx = nullptr, bool refetch_only = false) {
   const int kb = a->planes->key_msb_bits;      // (the value width follows: supported profiles are (4, 8), (8, 8), (6, 6))
   const int d = a->head_dim;
   const int n_active = a->head_ids ? a->n_active_heads : a->heads;
@@ -862,7 +856,7 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
 #define SPATTEN_PQV(DD, KB, VB)                                                                     \
   do {                                                                                              \
     if constexpr (sizeof(T) < 4 && KB != 6) {                                                       \
-      if (qx) return launch_pqv<T, DD, KB, VB, false, true>(p, n_active, dyn, msb_only, st);        \
+      if (qx) return launch_pqv<T, DD, KB, VB, false, true>(p, n_active, dyn, msb_only, st, refetch_only); \
     }                                                                                               \
     return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, st)                     \
               : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, st);                          \
@@ -1063,11 +1057,12 @@ static int run_pq_local_v(const spatten_pq_local_v_args_t* la, const PlanesDev& 
   return launch_pqlv_gather<T, 64>(g, a->planes->value_bits, S, n_active, a->batch, st);
 }
 
-}  // namespace spatten
+int pq_qint_refetch(const spatten_pq_decode_args_t* a, const PlanesDev& pd, const PqQintExtra& qx, hipStream_t st) {
+  if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, st, nullptr, &qx, true);
+  return run_pqv<f16_t>(a, pd, st, nullptr, &qx, true);
+}
 
-using namespace spatten;
-
-static int pq_validate(const spatten_pq_decode_args_t* a, PlanesDev& pd) {
+int pq_validate(const spatten_pq_decode_args_t* a, PlanesDev& pd) {
   if (!a || a->struct_size != sizeof(spatten_pq_decode_args_t)) return SPATTEN_ERR_INVALID;
   if (!a->q || !a->out || !a->cos || !a->sin || !a->need_lsb || !planes_to_dev(a->planes, pd)) return SPATTEN_ERR_INVALID;
   if (a->batch <= 0 || a->heads <= 0 || a->kv_heads <= 0 || a->heads % a->kv_heads != 0 || a->kv_len <= 0) return SPATTEN_ERR_INVALID;
@@ -1082,6 +1077,10 @@ static int pq_validate(const spatten_pq_decode_args_t* a, PlanesDev& pd) {
   if (!pq_profile_supported(a->planes->key_msb_bits, a->planes->value_bits)) return SPATTEN_ERR_UNSUPPORTED;
   return SPATTEN_OK;
 }
+
+}  // namespace spatten
+
+using namespace spatten;
 
 extern "C" int spatten_attn_decode_pq(const spatten_pq_decode_args_t* a, void* stream) {
   PlanesDev pd;

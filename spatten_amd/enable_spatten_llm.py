@@ -26,7 +26,7 @@ _FAMILIES: Dict[str, Callable] = {"llama": _patch_llama}
 def enable_spatten_llm(model, start_size, important_size, recent_size, importance_mode="reference",
                        prefill_stash=True, assume_causal=False, head_keep=None, pq_threshold=None, local_v_keep=None,
                        layer_keep=None, fuse_qkv=False, native_gemv=False, head_parallel=None, numerics="auto",
-                       auto_graph=False, pq_profile=None, fused_step=False, token_scope="head", pq_query_bits=None):
+                       auto_graph=False, pq_profile=None, fused_step=False, token_scope="head", pq_query_bits=None, pq_grouped=False):
     """The reference's four positional arguments (enable_spatten_llm.py:5) plus opt-in extensions:
 
     ``prefill_stash=False``: forwards with ``q_len > 1`` do not materialise ``self.attn_scores`` ([B,H,q,N]: 4 GiB per
@@ -78,7 +78,10 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
     (4..8, with ``pq_profile`` (8, 8) or (4, 8) and without ``local_v_keep``: the rotated query quantised once per head, the keys
     scored with integer dot products — the RTL's fixed-point product, the traces' ``quant_query_bit``; None = the query stays in the
     model dtype.  Not a speed option: measured 3-6 % slower than the 16-bit query at 40 heads x 8192 rows, DESIGN 3.7 — it
-    reproduces the accelerator's arithmetic), ``local_v_keep``
+    reproduces the accelerator's arithmetic), ``pq_grouped`` (with ``pq_query_bits`` and ``pq_profile`` (8, 8), without ``head_keep``
+    / ``local_v_keep``, on a grouped-query model with head_dim 128: the MSB pass streams the planes once per KV head and scores the
+    head's group on the int8 matrix cores — spatten_attn_decode_pq_qint_gqa; a model outside that rule raises at its first
+    step), ``local_v_keep``
     (local V pruning at decode: fraction of the keys whose V row is fetched; together with ``pq_profile`` the composed step over
     the quantised planes — MSB scores, LSB refetch, V only for the kept keys from the quantised V plane — which also carries
     ``importance_mode="cascade"`` and ``head_keep`` and is captured by ``auto_graph``; ``local_v_keep=1.0`` keeps every V row and is
@@ -105,6 +108,9 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
     if pq_query_bits is not None and (pq_profile is None or tuple(int(x) for x in pq_profile) not in ((8, 8), (4, 8))
                                       or local_v_keep is not None):
         raise ValueError("pq_query_bits needs pq_profile (8, 8) or (4, 8) and no local_v_keep")
+    if pq_grouped and (pq_query_bits is None or pq_profile is None or tuple(int(x) for x in pq_profile) != (8, 8)
+                       or head_keep is not None or local_v_keep is not None):
+        raise ValueError("pq_grouped needs pq_query_bits and pq_profile (8, 8), and neither head_keep nor local_v_keep")
     prev_team = None
     if fused_step:
         import warnings
@@ -146,7 +152,8 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
 
         cache.ext = SpattenExtensions(cache, len(mods), cascade=importance_mode == "cascade", head_keep=head_keep,
                                       pq_threshold=pq_threshold, local_v_keep=local_v_keep, layer_keep=layer_keep,
-                                      head_parallel=head_parallel, pq_profile=pq_profile, pq_query_bits=pq_query_bits)
+                                      head_parallel=head_parallel, pq_profile=pq_profile, pq_query_bits=pq_query_bits,
+                                      pq_grouped=pq_grouped)
         for layer, m in enumerate(mods):
             m._spatten_ext = (cache.ext, layer)
     if auto_graph:

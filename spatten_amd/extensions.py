@@ -26,6 +26,10 @@ against those restatements.
     pq_query_bits=n             with pq_profile (8, 8) / (4, 8): the rotated query quantised to n bits (4..8) once per head and the
                                 keys scored with integer dot products (spatten_attn_decode_pq_qint; DotProduct.scala, the traces'
                                 quant_query_bit); the step's row is appended by spatten_kv_append_planes first
+    pq_grouped=True             with pq_query_bits and pq_profile (8, 8), on a grouped-query model (H / Hkv in [2, 32], head_dim
+                                128): the MSB pass streams the planes once per KV head and scores the group on the int8 matrix
+                                cores (spatten_attn_decode_pq_qint_gqa); no head_keep, no local_v_keep; a model outside the
+                                rule raises NotImplementedError at its first step
     pq_profile + local_v_keep   the whole cascade of the RTL in one decode step (spatten_attn_decode_pq_local_v): MSB scores,
                                 LSB refetch for the flagged heads, V fetched only for the kept keys and only from the quantised
                                 V plane, with or without importance_mode="cascade" (fused, deferred by one step as above) and
@@ -114,7 +118,17 @@ class SpattenExtensions:
     def __init__(self, cache, n_layers: int, cascade: bool = False,
                  head_keep: Union[None, int, Sequence[int]] = None, pq_threshold: Optional[float] = None,
                  local_v_keep: Optional[float] = None, layer_keep: Optional[Sequence[int]] = None, head_parallel=None,
-                 pq_profile: Optional[Sequence[int]] = None, pq_query_bits: Optional[int] = None):
+                 pq_profile: Optional[Sequence[int]] = None, pq_query_bits: Optional[int] = None, pq_grouped: bool = False):
+        if pq_grouped:
+            if pq_query_bits is None or pq_profile is None or tuple(int(x) for x in pq_profile) != (8, 8):
+                raise ValueError("pq_grouped needs pq_query_bits and pq_profile (8, 8) (the grouped MSB pass scores the 8-bit "
+                                 "plane on the int8 matrix cores)")
+            if head_keep is not None:
+                raise ValueError("pq_grouped cannot be combined with head_keep (a workgroup column is a KV head: head pruning "
+                                 "takes the per-head form)")
+            if local_v_keep is not None:
+                raise ValueError("pq_grouped cannot be combined with local_v_keep (the composed local-V step has no grouped form)")
+        self.pq_grouped = bool(pq_grouped)
         if pq_query_bits is not None:
             if pq_profile is None or tuple(int(x) for x in pq_profile) not in ((8, 8), (4, 8)):
                 raise ValueError("pq_query_bits needs pq_profile (8, 8) or (4, 8) (the integer-dot decode has no (6, 6) form)")
@@ -247,7 +261,8 @@ class SpattenExtensions:
             ops.attn_decode_pqv(q, slab.pq, cap, cos, sin, 0, self.pq_threshold, out=st.out, need_lsb=st.need_lsb,
                                 scores=st.stash[0], lse=st.lse[0], head_ids=st.head_ids,
                                 head_abs=st.head_abs if self.head_keep is not None else None, step=step, append=app,
-                                query_bits=qb, q_quant=None if qb is None else st.ensure_q_quant(B, H, d, q.device))
+                                query_bits=qb, q_quant=None if qb is None else st.ensure_q_quant(B, H, d, q.device),
+                                grouped=self.pq_grouped)
             return st.out, st.stash[0][:, :, None, :kv_len]
         if self.pq_threshold is not None:
             # rows [0, kv_len - 1) packed with host lengths BEFORE the capture (the eager first step of the binding does it:
@@ -310,7 +325,8 @@ class SpattenExtensions:
             slab.pq_len = kv_len
             ops.attn_decode_pqv(q, slab.pq, kv_len, cos, sin, past_len, self.pq_threshold, out=st.out, need_lsb=st.need_lsb,
                                 scores=stash, lse=lse, head_ids=st.head_ids, head_abs=head_abs, layout=slab.capacity, append=app,
-                                query_bits=qb, q_quant=None if qb is None else st.ensure_q_quant(B, H, d, q.device))
+                                query_bits=qb, q_quant=None if qb is None else st.ensure_q_quant(B, H, d, q.device),
+                                grouped=self.pq_grouped)
         elif self.pq_threshold is not None:
             ops.kv_append(k_new[:, :, None], v_new[:, :, None], slab.k, slab.kr, slab.v, past_len, cos, sin)
             slab.ensure_pq(kv_len)

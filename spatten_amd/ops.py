@@ -1429,7 +1429,7 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
                     head_ids: Optional[torch.Tensor] = None, head_abs: Optional[torch.Tensor] = None,
                     step: Optional["StepState"] = None, layout: int = 0, n_splits: int = 0, msb_only: bool = False,
                     workspace: Optional[DecodeWorkspace] = None, append=None, query_bits: Optional[int] = None,
-                    q_quant: Optional[tuple] = None) -> torch.Tensor:
+                    q_quant: Optional[tuple] = None, grouped: bool = False) -> torch.Tensor:
     """Decode over the profiled planes (spatten_attn_decode_pq): MSB pass + LSB-only refetch for the flagged heads, P.V over
     the quantised values.  q [B,H,d]; returns out [B, H*d]; ``need_lsb`` int32 [B*H] is written.
     ``append`` = (k_new, v_new, k_cache | None, kr_cache, v_cache): the step's append INSIDE the MSB pass (round 5) — row kv_len - 1
@@ -1437,7 +1437,13 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
     ``query_bits`` (4..8; None: the query stays in the model dtype): the quantised-query form (spatten_attn_decode_pq_qint) —
     the rotated query quantised once per head, every key scored with integer dot products.  ``q_quant`` = (q_int int8 [B,H,d],
     q_scale fp32 [B,H]) receives the quantised query of the launched heads (allocated when absent).  f16 / bf16, profiles (8, 8)
-    and (4, 8); no ``append`` (call ``kv_append_planes`` first)."""
+    and (4, 8); no ``append`` (call ``kv_append_planes`` first).
+    ``grouped`` (needs ``query_bits``): the grouped-query form (spatten_attn_decode_pq_qint_gqa) — the MSB pass streams the planes
+    once per KV head and scores the head's whole group on the int8 matrix cores; same results (q_int, q_scale, msb_logit and the
+    MSB-only stash bit for bit, out / lse to rounding).  f16 / bf16, G = H / Hkv in [2, 32], head_dim 128, profile (8, 8); no
+    ``head_ids`` / ``head_abs``."""
+    if grouped and query_bits is None:
+        raise ValueError("attn_decode_pqv(grouped=True) is a form of the quantised-query decode: pass query_bits (4..8)")
     if query_bits is not None:
         if append is not None:
             raise NotImplementedError("attn_decode_pqv(query_bits=...) does not append inside the launch: call "
@@ -1448,6 +1454,16 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
             raise NotImplementedError(f"attn_decode_pqv(query_bits=...): {q.dtype}, head_dim {q.shape[2]}, profile "
                                       f"{(planes.key_bits, planes.value_bits)} has no quantised-query kernel (f16 / bf16, head_dim "
                                       "64 / 128, profiles (8, 8) and (4, 8))")
+        if grouped:
+            if head_ids is not None or head_abs is not None:
+                raise NotImplementedError("attn_decode_pqv(grouped=True) takes no head_ids / head_abs: a workgroup column is a KV "
+                                          "head — head pruning takes the per-head form (grouped=False)")
+            if not pq_qint_gqa_supported(q.dtype, q.shape[1], planes.msb.shape[1], q.shape[2], planes.key_bits, planes.value_bits,
+                                         int(query_bits)):
+                raise NotImplementedError(f"attn_decode_pqv(grouped=True): {q.dtype}, {q.shape[1]} / {planes.msb.shape[1]} heads, "
+                                          f"head_dim {q.shape[2]}, profile {(planes.key_bits, planes.value_bits)} is outside the "
+                                          "grouped rule (f16 / bf16, H % Hkv == 0 with G = H / Hkv in [2, 32], head_dim 128, "
+                                          "profile (8, 8), query_bits in [4, 8])")
     _dev(q, planes.msb, cos, sin, out, need_lsb, scores, lse, head_ids, head_abs)
     B, H, d = q.shape
     Hkv = planes.msb.shape[1]
@@ -1509,6 +1525,9 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
         qa.step = a
         qa.q_int, qa.qi_sb, qa.qi_sh = q_int.data_ptr(), q_int.stride(0), q_int.stride(1)
         qa.q_scale = q_scale.data_ptr()
+        if grouped:
+            _lib.check(_lib.load().spatten_attn_decode_pq_qint_gqa(ctypes.byref(qa), stream), "spatten_attn_decode_pq_qint_gqa")
+            return out
         _lib.check(_lib.load().spatten_attn_decode_pq_qint(ctypes.byref(qa), stream), "spatten_attn_decode_pq_qint")
         return out
     _lib.check(_lib.load().spatten_attn_decode_pq(ctypes.byref(a), stream), "spatten_attn_decode_pq")
@@ -1522,6 +1541,17 @@ def pq_qint_supported(dtype: torch.dtype, head_dim: int, key_bits: int, value_bi
     if code is None:
         return False
     return bool(_lib.load().spatten_pq_qint_supported(code, int(head_dim), int(key_bits), int(value_bits), int(query_bits)))
+
+
+def pq_qint_gqa_supported(dtype: torch.dtype, heads: int, kv_heads: int, head_dim: int, key_bits: int, value_bits: int,
+                          query_bits: int) -> bool:
+    """Whether ``attn_decode_pqv(..., query_bits=, grouped=True)`` takes this geometry (spatten_pq_qint_gqa_supported: host rule, no
+    GPU): f16 / bf16, heads % kv_heads == 0 with G = heads / kv_heads in [2, 32], head_dim 128, profile (8, 8), query_bits in [4, 8]."""
+    code = _DT.get(dtype)
+    if code is None:
+        return False
+    return bool(_lib.load().spatten_pq_qint_gqa_supported(code, int(heads), int(kv_heads), int(head_dim), int(key_bits),
+                                                          int(value_bits), int(query_bits)))
 
 
 _pqlv_ws_cache = _LRU(8)
