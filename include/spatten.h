@@ -688,6 +688,35 @@ typedef struct spatten_pq_local_v_args {
 size_t spatten_pq_local_v_workspace_bytes(int batch, int heads, int head_dim, int max_kv_len);
 int spatten_attn_decode_pq_local_v(const spatten_pq_local_v_args_t* args, void* stream);
 
+/* spatten_attn_decode_pq with the cumulative token importance (README.md:11) folded into its two launches: progressive quantisation
+ * and cascade ranking in one step, every V row read (no local V pruning — that is spatten_attn_decode_pq_local_v).  out, the stash,
+ * lse, need_lsb and head_abs_acc are bit-identical to spatten_attn_decode_pq on the same inputs.  Parity unpinned, as above.
+ *   step            the step exactly as spatten_attn_decode_pq takes it; lse required.  Both length forms, head_ids, head_abs_acc,
+ *                   grouped-query caches (kv_heads < heads), every dtype, head_dim and profile of spatten_attn_decode_pq
+ *   importance_acc  [H, >= kv_len] fp32, stride acc_sh, required.  The fold is deferred by one step like spatten_decode_args_t's:
+ *                   while the MSB pass streams the keys, the thread about to overwrite msb_logit[b,h,j] first adds
+ *                   exp(old - prev_lse[unit, 0]) / prev_lse[unit, 1] to acc[h, j] for j < prev_len (step_state: state word 3; a
+ *                   -inf max counts as 0) — the previous step's probability, by the expression spatten_importance_accumulate
+ *                   uses: a step folded here and a step folded by the flush add the same bits.  One add per (b, h, j) and step
+ *                   (batch > 1: the adds of one element are atomic, their order is not fixed).  prev_len = 0: nothing is folded
+ *   prev_lse        [B*H, 2] fp32, in / out, required: read at the top of the MSB pass, and this step's (max, sum) of every launched
+ *                   unit when the call returns (= lse) — the caller keeps ONE buffer and passes it to every step
+ *   msb_logit       after the call: the fp32 logits the output was computed from, for every launched head — the MSB-only logits of
+ *                   a confident head, the final (MSB + LSB) logits of a flagged one (the refetch pass writes them back; the plain
+ *                   step leaves a flagged head's MSB-only logits there)
+ * The last step before a prune has not been folded yet: spatten_importance_accumulate(SPATTEN_F32, msb_logit, lse) flushes it.
+ * Pruned heads (step.head_ids) are not launched: their rows of acc / prev_lse / out / stash / lse are left untouched.
+ * SPATTEN_ERR_INVALID: as spatten_attn_decode_pq; NULL importance_acc / prev_lse / step.lse / msb_logit; prev_len < 0; prev_len >
+ * kv_len in the host form; a wrong struct_size.  SPATTEN_ERR_UNSUPPORTED: step.k_new set (append with spatten_kv_append_planes
+ * first).  The quantised-query and grouped forms below have no cascade variant. */
+typedef struct spatten_pq_cascade_args {
+  uint32_t struct_size; int32_t prev_len;          /* sizeof(spatten_pq_cascade_args_t); host form — ignored with step.step_state */
+  spatten_pq_decode_args_t step;
+  float* importance_acc; int64_t acc_sh;
+  float* prev_lse;
+} spatten_pq_cascade_args_t;
+int spatten_attn_decode_pq_cascade(const spatten_pq_cascade_args_t* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Quantised query: the decode step over the planes with integer dot products (opt-in; parity unpinned — the RTL multiplies
  * fixed point by fixed point, DotProduct.scala, and the traces carry the width as quant_query_bit).  spatten_attn_decode_pq with

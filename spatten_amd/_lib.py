@@ -117,6 +117,16 @@ class PQLocalVArgs(ctypes.Structure):
     ]
 
 
+class PQCascadeArgs(ctypes.Structure):
+    """``spatten_pq_cascade_args_t`` (include/spatten.h): the profiled step with the cascade importance folded into its launches."""
+    _fields_ = [
+        ("struct_size", c_uint32), ("prev_len", c_int32),
+        ("step", PQDecodeArgs),
+        ("importance_acc", c_void_p), ("acc_sh", c_int64),
+        ("prev_lse", c_void_p),
+    ]
+
+
 class PQQintArgs(ctypes.Structure):
     """``spatten_pq_qint_args_t`` (include/spatten.h): the profiled step with a quantised query (integer dot products)."""
     _fields_ = [
@@ -217,6 +227,8 @@ def _declare(lib):
     lib.spatten_pq_local_v_workspace_bytes.argtypes = [i, i, i, i]
     lib.spatten_attn_decode_pq_local_v.restype = c_int
     lib.spatten_attn_decode_pq_local_v.argtypes = [POINTER(PQLocalVArgs), p]
+    lib.spatten_attn_decode_pq_cascade.restype = c_int
+    lib.spatten_attn_decode_pq_cascade.argtypes = [POINTER(PQCascadeArgs), p]
     lib.spatten_attn_decode_pq_qint.restype = c_int
     lib.spatten_attn_decode_pq_qint.argtypes = [POINTER(PQQintArgs), p]
     lib.spatten_pq_qint_supported.restype = c_int

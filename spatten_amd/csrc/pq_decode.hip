@@ -59,7 +59,10 @@ struct PqvParams {
   // the SCORES-ONLY form (SO: local V pruning over the planes, spatten_attn_decode_pq_local_v): the MSB pass folds the previous
   // step's probabilities into acc[h, j] (j < prev_len; DYN: state word 3) from the fp32 logits that step left in msb_logit and its
   // (max, sum) in prev_lse — read before this pass overwrites the row, by the thread that overwrites it
-  float* acc; int64_t acc_sh; const float* prev_lse; int prev_len;
+  // the CASCADE form of the full step (CF, spatten_attn_decode_pq_cascade): the same fold inside the full MSB pass; the refetch pass
+  // writes the flagged heads' final logits back to msb_logit, and the merging workgroup of either pass publishes the unit's (max, sum)
+  // to prev_lse (the kernel comment carries the ordering argument)
+  float* acc; int64_t acc_sh; float* prev_lse; int prev_len;
   // the QUANTISED QUERY form (QI, spatten_attn_decode_pq_qint): the rotated query quantised once per head to qmax = 2^(query_bits-1) - 1
   // levels, every key scored with integer dot products; split 0 of the MSB pass exports q_int [B,H,d] (element order) and q_scale [B,H]
   int8_t* qi_out; int64_t qi_sb, qi_sh; float* qs_out; int qmax;
@@ -224,9 +227,25 @@ template <int KBITS, int W> __device__ inline int qint_dot(const uint32_t (&w)[W
 // SO (scores only): no V traffic and no output — the stash, the fp32 logits (msb_logit: pass 1 all heads, the refetch pass
 // rewrites the flagged heads' rows with their final logits), lse and need_lsb; the kept-row select and the gather follow
 // QI: the quantised-query form — only the prologue (quantise, pack, export) and the per-row logit differ
-template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false, bool QI = false>
+// CF (cascade fold, spatten_attn_decode_pq_cascade): the FULL step with SO's fold — its own instantiation, as APP is and for APP's
+// reason: every other instantiation keeps its code.  The MSB pass adds the previous step's probability of row j to acc[h, j] before it
+// overwrites msb_logit[b, h, j] (the row's c == 0 thread, rows j < prev_len of its split: ONE add per (b, h, j) and step); the refetch
+// pass leaves the flagged heads' final logits in msb_logit, so after the step msb_logit holds the logits the output came from.
+// prev_lse is ONE buffer, read and written in the same step:
+//   MSB pass: every wave of every split loads prev_lse[unit] before its first tile and consumes it no later than its last tile (the
+//   fold is the only reader).  A workgroup publishes its partial only behind the __syncthreads() that follows every wave's last
+//   tile, and the merging workgroup — the last split (polling form) or the last arriver (ticket form) — stores prev_lse[unit] only
+//   after it has SEEN every split's partial carry this launch's tag.  A store issued after the loads' values were consumed cannot
+//   reach them: the merger's store is ordered behind every read of the unit.  One split: the same __syncthreads().
+//   Refetch pass (the compact grid included): it never READS prev_lse — it folds nothing — and it starts after the MSB pass has
+//   ended (stream order), so its merger's store needs no argument inside the launch; which split merges does not matter.
+// The MSB pass publishes for every head (the MSB-only statistics, final for a confident head), the refetch pass overwrites the
+// flagged ones: exactly the two stores `lse` sees.
+template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false, bool QI = false,
+          bool CF = false>
 __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams<T> p_in) {
   static_assert(!QI || (sizeof(T) < 4 && KB != 6 && !APP && !SO), "the quantised-query form: 16-bit dtypes, (8, 8) / (4, 8), no append, full P.V");
+  static_assert(!CF || (!APP && !SO && !QI), "the cascade form: the full step, no in-launch append, fp32 query");
   PqvParams<T> p = p_in;                         // (the compact refetch pass picks its split layout by the number of flagged heads)
   constexpr int LPR = D / 16;                    // lanes per row: lane c owns the row's piece c (16 elements)
   constexpr int RPI = kPqvThreads / LPR;         // rows per row-group
@@ -280,7 +299,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
 
   int n_dyn = 0, pl_dyn = 0;
   if (DYN) n_dyn = p.step[opaque_lane(0)];       // requested FIRST (in-order returns), read after the tile loads went out
-  constexpr bool fold = SO && PASS == 1;         // (the cascade fold: prev_len = 0 / acc == NULL turn it off at run time)
+  constexpr bool fold = (SO || CF) && PASS == 1;       // (the cascade fold: prev_len = 0 / acc == NULL turn it off at run time)
   float prev_ml[2] = {0.f, 1.f};
   if (fold) {
     if (DYN) pl_dyn = p.step[3 + opaque_lane(0)];
@@ -297,7 +316,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   const __amdgpu_buffer_rsrc_t rs_v = make_rsrc(p.pl.vq + b * p.pl.vq_sb + hkv * p.pl.vq_sh, (int64_t)rl * VROW);
   const __amdgpu_buffer_rsrc_t rs_vs = make_rsrc(p.pl.vs + b * p.pl.sc_sb + hkv * p.pl.sc_sh, (int64_t)rl * 4);
   // (the fold's old logits: a descriptor of 0 records when nothing is folded — the loads then touch no memory)
-  const __amdgpu_buffer_rsrc_t rs_lg = make_rsrc(lgb, (PASS == 2 || (fold && p.acc != nullptr)) ? (int64_t)rl * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rs_lg = make_rsrc(lgb, (PASS == 2 || (fold && p.acc != nullptr && (!CF || DYN || p.prev_len > 0))) ? (int64_t)rl * 4 : 0);
   // Rows of a tile (round 5): thread-row r owns the UP CONSECUTIVE rows t0 + r UP + u (r04: t0 + u RPI + r) — a wave's rows of a
   // tile are then one contiguous run, the UP row scales of a lane are ONE 16-byte load per plane (r04: a 4-byte load per
   // row-group and plane — half of the kernel's memory instructions carried 32 bytes per wave), and a lane's UP stash entries /
@@ -422,7 +441,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   // the bounds check) and whose per-lane offset is out of range for every lane but the row's first (c != 0)
   T* stashp = p.scores ? p.scores + b * p.sc_sb + h * p.sc_sh : nullptr;
   const __amdgpu_buffer_rsrc_t rs_st = make_rsrc(stashp, stashp ? (int64_t)hi * (int64_t)sizeof(T) : 0);
-  const __amdgpu_buffer_rsrc_t rs_lgw = make_rsrc(lgb, (PASS == 1 || SO) ? (int64_t)hi * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rs_lgw = make_rsrc(lgb, (PASS == 1 || SO || CF) ? (int64_t)hi * 4 : 0);
   const int prev_len = !fold ? 0 : (p.acc == nullptr) ? 0 : DYN ? __builtin_amdgcn_readfirstlane(pl_dyn) : p.prev_len;
   float* accp = (fold && p.acc != nullptr) ? p.acc + h * p.acc_sh : nullptr;
   // (exp / sum with a true division: the same bits as spatten_importance_accumulate's fold of the same row, so a step folded
@@ -521,7 +540,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
         }
         bstore<UP / 2>(rs_st, vo_st, t0 * 2, sw);
       }
-      if (PASS == 1 || SO) bstore<UP>(rs_lgw, vo_lw, t0 * 4, lw);
+      if (PASS == 1 || SO || CF) bstore<UP>(rs_lgw, vo_lw, t0 * 4, lw);
     } else {
 #pragma unroll
       for (int u = 0; u < UP; ++u) {
@@ -532,7 +551,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
           const T sv = DT<T>::from_f32(s);
           __builtin_amdgcn_raw_buffer_store_b16(*reinterpret_cast<const unsigned short*>(&sv), rs_st, vo_st, (t0 + u) * 2, 0);
         }
-        if (PASS == 1 || SO) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(s), rs_lgw, vo_lw, (t0 + u) * 4, 0);
+        if (PASS == 1 || SO || CF) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(s), rs_lgw, vo_lw, (t0 + u) * 4, 0);
       }
     }
     float m_new = m_run;
@@ -634,6 +653,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   if (p.S == 1) {
     if (!SO && tid < D) outp[tid] = DT<T>::from_f32(o_tot / l_tot);
     if (p.lse != nullptr && tid == 0) { float* ls = p.lse + (int64_t)unit * 2; ls[0] = m_run; ls[1] = l_tot; }
+    if (CF && tid == 0) { float* ps = p.prev_lse + (int64_t)unit * 2; ps[0] = m_run; ps[1] = l_tot; }   // (behind the __syncthreads above)
     const bool need1 = PASS == 1 && (1.0f / l_tot) < p.thr;                              // max prob = exp(0) / sum
     if (PASS == 1 && tid == 0) p.need[unit] = need1 ? 1 : 0;
     if (!SO && p.head_abs != nullptr) add_head_abs(o_tot / l_tot, tid < D, !need1);
@@ -736,6 +756,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   }
   if (tid == 0) {
     if (p.lse != nullptr) { float* ls = p.lse + (int64_t)unit * 2; ls[0] = mg; ls[1] = lg; }
+    if (CF) { float* ps = p.prev_lse + (int64_t)unit * 2; ps[0] = mg; ps[1] = lg; }      // (every split's partial has landed: see the top)
     if (PASS == 1) p.need[unit] = (1.0f / lg) < p.thr ? 1 : 0;
     p.ws_cnt[2 * unit + 1] = gen + 1u;
     if (!p.poll_merge) __hip_atomic_store(p.ws_cnt + 2 * unit, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -752,17 +773,17 @@ template <typename K> static int resident_capacity(K kernel) {
   return std::max(1, std::min(per_cu, 2)) * cus;
 }
 
-template <typename T, int D, int KB, int VB, bool SO = false, bool QI = false>
+template <typename T, int D, int KB, int VB, bool SO = false, bool QI = false, bool CF = false>
 static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st, bool refetch_only = false) {
   const bool app = p.k_new != nullptr;
   constexpr int UP = kPqvUp;
   const dim3 grid((unsigned)p.S, (unsigned)n_active, (unsigned)p.B), blk(kPqvThreads);
   // (the pass-1 and pass-2 kernels of a profile have different register footprints: the smaller capacity decides)
-  // (QI: its own kernels' answer; their register footprint is not the fp32-query kernels')
-  static const int cap_static = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, QI>),
-                                         resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, QI>));
-  static const int cap_dyn = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, QI>),
-                                      resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, QI>));
+  // (QI, CF: their own kernels' answer; their register footprint is not the plain kernels')
+  static const int cap_static = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, QI, CF>),
+                                         resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, QI, CF>));
+  static const int cap_dyn = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, QI, CF>),
+                                      resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, QI, CF>));
   p.poll_merge = (p.S > 1 && (long long)p.S * n_active * p.B <= (dyn ? cap_dyn : cap_static)) ? 1 : 0;
   // ---- the refetch pass (round 6): at the reference traces' rate 2-3 of 30 heads are flagged per layer-step; laid out like pass 1
   // their rows sit on S CUs each and the pass takes as long as if every head were flagged (a CU streams at ~21 B/ns).  So pass 2
@@ -791,6 +812,15 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
       if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, true>), grid2, blk, 0, st, p2);
     }
     return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
+  } else if constexpr (CF) {   // (no append: spatten_attn_decode_pq_cascade refuses it)
+    if (dyn) {
+      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, false, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, false, true>), grid2, blk, 0, st, p2);
+    } else {
+      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, false, UP, false, false, false, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, false, true>), grid2, blk, 0, st, p2);
+    }
+    return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
   } else
   if (dyn) {
     if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, true, SO>), grid, blk, 0, st, p);
@@ -804,8 +834,9 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
   return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
 }
 
-// the local-V extras of spatten_attn_decode_pq_local_v (NULL: the plain profiled step)
-struct PqLvExtra { float* acc; int64_t acc_sh; const float* prev_lse; int prev_len; };
+// the local-V extras of spatten_attn_decode_pq_local_v (NULL: the plain profiled step); full: spatten_attn_decode_pq_cascade — the
+// fold inside the FULL step (the CF instantiations) instead of the scores-only passes
+struct PqLvExtra { float* acc; int64_t acc_sh; float* prev_lse; int prev_len; bool full; };
 
 template <typename T>
 static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st, const PqLvExtra* lv = nullptr,
@@ -858,6 +889,7 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
     if constexpr (sizeof(T) < 4 && KB != 6) {                                                       \
       if (qx) return launch_pqv<T, DD, KB, VB, false, true>(p, n_active, dyn, msb_only, st, refetch_only); \
     }                                                                                               \
+    if (lv && lv->full) return launch_pqv<T, DD, KB, VB, false, false, true>(p, n_active, dyn, msb_only, st); \
     return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, st)                     \
               : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, st);                          \
   } while (0)
@@ -1040,7 +1072,7 @@ static int run_pq_local_v(const spatten_pq_local_v_args_t* la, const PlanesDev& 
   float* part = (float*)((char*)la->workspace + lv_cnt_bytes(units));
   int32_t* idx = (int32_t*)((char*)part + units * kLvMaxSplits * (size_t)a->head_dim * sizeof(float));
 
-  PqLvExtra ex{la->importance_acc, la->acc_sh, la->prev_lse, la->prev_len};
+  PqLvExtra ex{la->importance_acc, la->acc_sh, la->prev_lse, la->prev_len, false};
   int rc = run_pqv<T>(a, pd, st, &ex);                           // MSB pass + refetch pass, scores only
   if (rc != SPATTEN_OK) return rc;
   const int32_t* step = (const int32_t*)a->step_state;
@@ -1089,6 +1121,21 @@ extern "C" int spatten_attn_decode_pq(const spatten_pq_decode_args_t* a, void* s
   if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream);
   if (a->dtype == SPATTEN_F16) return run_pqv<f16_t>(a, pd, (hipStream_t)stream);
   return run_pqv<float>(a, pd, (hipStream_t)stream);
+}
+
+extern "C" int spatten_attn_decode_pq_cascade(const spatten_pq_cascade_args_t* ca, void* stream) {
+  if (!ca || ca->struct_size != sizeof(spatten_pq_cascade_args_t)) return SPATTEN_ERR_INVALID;
+  const spatten_pq_decode_args_t* a = &ca->step;
+  PlanesDev pd;
+  const int rc = pq_validate(a, pd);
+  if (rc != SPATTEN_OK) return rc;
+  if (!ca->importance_acc || !ca->prev_lse || !a->lse || !pd.lg) return SPATTEN_ERR_INVALID;
+  if (ca->prev_len < 0 || (!a->step_state && ca->prev_len > a->kv_len)) return SPATTEN_ERR_INVALID;
+  if (a->k_new != nullptr) return SPATTEN_ERR_UNSUPPORTED;       // append with spatten_kv_append_planes first
+  PqLvExtra ex{ca->importance_acc, ca->acc_sh, ca->prev_lse, ca->prev_len, true};
+  if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream, &ex);
+  if (a->dtype == SPATTEN_F16) return run_pqv<f16_t>(a, pd, (hipStream_t)stream, &ex);
+  return run_pqv<float>(a, pd, (hipStream_t)stream, &ex);
 }
 
 extern "C" int spatten_pq_qint_supported(int dtype, int head_dim, int key_msb_bits, int value_bits, int query_bits) {

@@ -26,7 +26,8 @@ _FAMILIES: Dict[str, Callable] = {"llama": _patch_llama}
 def enable_spatten_llm(model, start_size, important_size, recent_size, importance_mode="reference",
                        prefill_stash=True, assume_causal=False, head_keep=None, pq_threshold=None, local_v_keep=None,
                        layer_keep=None, fuse_qkv=False, native_gemv=False, head_parallel=None, numerics="auto",
-                       auto_graph=False, pq_profile=None, fused_step=False, token_scope="head", pq_query_bits=None, pq_grouped=False):
+                       auto_graph=False, pq_profile=None, fused_step=False, token_scope="head", pq_query_bits=None, pq_grouped=False,
+                       pq_cascade=False):
     """The reference's four positional arguments (enable_spatten_llm.py:5) plus opt-in extensions:
 
     ``prefill_stash=False``: forwards with ``q_len > 1`` do not materialise ``self.attn_scores`` ([B,H,q,N]: 4 GiB per
@@ -85,7 +86,12 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
     (local V pruning at decode: fraction of the keys whose V row is fetched; together with ``pq_profile`` the composed step over
     the quantised planes — MSB scores, LSB refetch, V only for the kept keys from the quantised V plane — which also carries
     ``importance_mode="cascade"`` and ``head_keep`` and is captured by ``auto_graph``; ``local_v_keep=1.0`` keeps every V row and is
-    how a profile combines with cascade importance), ``layer_keep`` (layer-to-layer cascade token
+    one way a profile combines with cascade importance), ``pq_cascade`` (with ``pq_profile`` and ``importance_mode="cascade"``,
+    without ``local_v_keep`` / ``pq_query_bits`` / ``pq_grouped``: the profiled decode step with the cumulative importance folded
+    into its two launches — spatten_attn_decode_pq_cascade; every V row is read and there is no select / gather launch; carries
+    ``head_keep`` and is captured by ``auto_graph``.  Measured 29.4 us per layer-step against 74.9 for
+    ``local_v_keep=1.0`` and 26.1 for the profiled step without importance, 40 heads x 8192 rows, DESIGN 3.7: the route to prefer when
+    every V row is kept), ``layer_keep`` (layer-to-layer cascade token
     pruning: one important-token count per layer, non-increasing — the surviving set shrinks through the layers),
     ``token_scope="global"`` (ONE kept token set per layer shared by all heads, ranked by the importance summed over the
     heads — README.md:21, workloads/small.csv:1; head-parallel ranks all-reduce the [layers, L] sums once per prune event;
@@ -111,6 +117,10 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
     if pq_grouped and (pq_query_bits is None or pq_profile is None or tuple(int(x) for x in pq_profile) != (8, 8)
                        or head_keep is not None or local_v_keep is not None):
         raise ValueError("pq_grouped needs pq_query_bits and pq_profile (8, 8), and neither head_keep nor local_v_keep")
+    if pq_cascade and (pq_profile is None or importance_mode != "cascade" or local_v_keep is not None
+                       or pq_query_bits is not None or pq_grouped):
+        raise ValueError("pq_cascade needs pq_profile and importance_mode='cascade', and none of local_v_keep / pq_query_bits / "
+                         "pq_grouped")
     prev_team = None
     if fused_step:
         import warnings
@@ -153,7 +163,7 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
         cache.ext = SpattenExtensions(cache, len(mods), cascade=importance_mode == "cascade", head_keep=head_keep,
                                       pq_threshold=pq_threshold, local_v_keep=local_v_keep, layer_keep=layer_keep,
                                       head_parallel=head_parallel, pq_profile=pq_profile, pq_query_bits=pq_query_bits,
-                                      pq_grouped=pq_grouped)
+                                      pq_grouped=pq_grouped, pq_cascade=pq_cascade)
         for layer, m in enumerate(mods):
             m._spatten_ext = (cache.ext, layer)
     if auto_graph:

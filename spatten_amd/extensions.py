@@ -33,8 +33,11 @@ against those restatements.
     pq_profile + local_v_keep   the whole cascade of the RTL in one decode step (spatten_attn_decode_pq_local_v): MSB scores,
                                 LSB refetch for the flagged heads, V fetched only for the kept keys and only from the quantised
                                 V plane, with or without importance_mode="cascade" (fused, deferred by one step as above) and
-                                head_keep.  local_v_keep=1.0 runs this path with every V row kept — the way to combine a
+                                head_keep.  local_v_keep=1.0 runs this path with every V row kept — one way to combine a
                                 profile with cascade importance.
+    pq_profile + pq_cascade     the profiled step with the cumulative importance folded into its two launches
+                                (spatten_attn_decode_pq_cascade): importance_mode="cascade" on the profiled planes with every V row
+                                read and no select / gather launches; with or without head_keep
     layer_keep=[k_0..k_L-1]     layer-to-layer cascade token pruning (README.md:11; the traces' key_fetch_num shrinks layer
                                 by layer): at a prune event layer l keeps k_l tokens of its window, chosen among the
                                 tokens layer l-1 just kept — the surviving set shrinks through the layers.  Caches of
@@ -118,7 +121,18 @@ class SpattenExtensions:
     def __init__(self, cache, n_layers: int, cascade: bool = False,
                  head_keep: Union[None, int, Sequence[int]] = None, pq_threshold: Optional[float] = None,
                  local_v_keep: Optional[float] = None, layer_keep: Optional[Sequence[int]] = None, head_parallel=None,
-                 pq_profile: Optional[Sequence[int]] = None, pq_query_bits: Optional[int] = None, pq_grouped: bool = False):
+                 pq_profile: Optional[Sequence[int]] = None, pq_query_bits: Optional[int] = None, pq_grouped: bool = False,
+                 pq_cascade: bool = False):
+        if pq_cascade:
+            if pq_profile is None or not cascade:
+                raise ValueError("pq_cascade needs pq_profile and importance_mode='cascade' (it is the profiled decode step with "
+                                 "the cumulative importance folded in)")
+            if local_v_keep is not None:
+                raise ValueError("pq_cascade cannot be combined with local_v_keep (the composed local-V step already accumulates)")
+            if pq_query_bits is not None or pq_grouped:
+                raise ValueError("pq_cascade cannot be combined with pq_query_bits / pq_grouped (the quantised-query steps do not "
+                                 "carry the fused accumulation)")
+        self.pq_cascade = bool(pq_cascade)
         if pq_grouped:
             if pq_query_bits is None or pq_profile is None or tuple(int(x) for x in pq_profile) != (8, 8):
                 raise ValueError("pq_grouped needs pq_query_bits and pq_profile (8, 8) (the grouped MSB pass scores the 8-bit "
@@ -145,10 +159,11 @@ class SpattenExtensions:
                 raise ValueError("pq_profile needs pq_threshold")
             if pq_profile not in ops.PQ_PROFILES:
                 raise ValueError(f"pq_profile {pq_profile}: one of {ops.PQ_PROFILES} (key MSB bits, value bits)")
-            if cascade and local_v_keep is None:
+            if cascade and local_v_keep is None and not pq_cascade:
                 raise ValueError("pq_profile with importance_mode='cascade': the profiled decode launch does not carry the fused "
                                  "accumulation — use the default planes (pq_profile=None), or local_v_keep (1.0 keeps every V "
-                                 "row) for the profiled local-V step, which does")
+                                 "row) for the profiled local-V step, which does, or pq_cascade=True for the profiled step with "
+                                 "the accumulation folded into its launches")
         self.pq_profile = pq_profile
         if pq_threshold is not None and local_v_keep is not None and pq_profile is None:
             raise ValueError("pq_threshold and local_v_keep cannot be combined on the default planes (the local-V pass scores "
@@ -185,8 +200,15 @@ class SpattenExtensions:
         layers decode on caches of different lengths: one step state per length).  Local V pruning is ONE launch whose kept
         count ceil(f * length) is evaluated on the device (round 4) — captured too, except together with cascade importance
         (its accumulation there runs on host lengths) — and the profiled local-V step (spatten_attn_decode_pq_local_v), whose
-        kept count and fused accumulation both follow the device length."""
+        kept count and fused accumulation both follow the device length.  The profiled step with the folded accumulation
+        (pq_cascade) reads the fold's row count from the device state too."""
         return self.local_v_keep is None or not self.cascade or self.pq_local_v
+
+    @property
+    def pq_logit_fold(self) -> bool:
+        """The steps over the profiled planes that carry cascade importance (the composed local-V step and pq_cascade): ONE
+        stash / lse pair, lse[1] = the previous step's (max, sum), the pending step's fp32 logits in the planes' msb_logit."""
+        return self.pq_local_v or self.pq_cascade
 
     @property
     def pq_local_v(self) -> bool:
@@ -234,6 +256,18 @@ class SpattenExtensions:
                                        need_lsb=st.need_lsb, keep_fraction=self.local_v_keep, head_ids=st.head_ids,
                                        head_abs=st.head_abs if self.head_keep is not None else None,
                                        cascade=(st.acc, st.lse[1], 0) if self.cascade else None, step=step, append=app)
+            return st.out, st.stash[0][:, :, None, :kv_len]
+        if self.pq_cascade:
+            # as above without the select / gather: the step's row by spatten_kv_append_planes (the fused launch appends nothing)
+            planes = self._pq_lv_planes(st, slab, kv_len - 1, H)
+            if planes.capacity < cap:
+                raise RuntimeError("progressive-quant planes smaller than the slab capacity")
+            ops.kv_append_planes(k_new, v_new, slab.k, slab.kr, slab.v, planes, 0, cos, sin, step=step)
+            slab.pq_len = kv_len
+            ops.attn_decode_pqv(q, planes, cap, cos, sin, 0, self.pq_threshold, out=st.out, need_lsb=st.need_lsb,
+                                scores=st.stash[0], lse=st.lse[0], head_ids=st.head_ids,
+                                head_abs=st.head_abs if self.head_keep is not None else None, step=step,
+                                cascade=(st.acc, st.lse[1], 0))
             return st.out, st.stash[0][:, :, None, :kv_len]
         if self.local_v_keep is not None:
             # local V pruning: the step's append in device-length form, then the one-launch step (the kept count follows the
@@ -297,7 +331,7 @@ class SpattenExtensions:
             if st.stash[0] is None:
                 continue
             if self.cascade:
-                st.parity = 0 if self.pq_local_v else steps & 1
+                st.parity = 0 if self.pq_logit_fold else steps & 1
                 st.pending_len = n if steps > 0 else st.pending_len
 
     def decode_step(self, layer: int, q, k_new, v_new, slab, kv_len: int, past_len: int, cos, sin):
@@ -307,6 +341,8 @@ class SpattenExtensions:
         st.ensure(B, H, d, kv_len, q.dtype, q.device, self.cascade)
         if self.pq_local_v:
             return self._decode_step_pq_local_v(st, q, k_new, v_new, slab, kv_len, past_len, cos, sin)
+        if self.pq_cascade:
+            return self._decode_step_pq_cascade(st, q, k_new, v_new, slab, kv_len, past_len, cos, sin)
         cur = st.parity
         st.parity ^= 1
         stash, lse = st.stash[cur], st.lse[cur]
@@ -376,6 +412,20 @@ class SpattenExtensions:
             st.pending_len = kv_len
         return st.out, st.stash[0][:, :, None, :kv_len]
 
+    def _decode_step_pq_cascade(self, st, q, k_new, v_new, slab, kv_len: int, past_len: int, cos, sin):
+        """The profiled step with the folded accumulation, host lengths: the buffers of the composed step (stash[0], lse[0]; lse[1]
+        = the previous step's (max, sum), refreshed by the launch; the pending logits in the planes' msb_logit)."""
+        B, H, d = q.shape
+        planes = self._pq_lv_planes(st, slab, past_len, H)
+        ops.kv_append_planes(k_new, v_new, slab.k, slab.kr, slab.v, planes, past_len, cos, sin)
+        slab.pq_len = kv_len
+        ops.attn_decode_pqv(q, planes, kv_len, cos, sin, past_len, self.pq_threshold, out=st.out, need_lsb=st.need_lsb,
+                            scores=st.stash[0], lse=st.lse[0], head_ids=st.head_ids,
+                            head_abs=st.head_abs if self.head_keep is not None else None, layout=slab.capacity,
+                            cascade=(st.acc, st.lse[1], min(st.pending_len, kv_len)))
+        st.pending_len = kv_len
+        return st.out, st.stash[0][:, :, None, :kv_len]
+
     def prefill_uses_pq(self, dtype, head_dim: int, q_len: int) -> bool:
         """The PQ-keyed flash kernel covers 16-bit dtypes at head_dim 64 / 128 and blocks of more than 8 rows (shorter
         blocks / fp32 run the exact rows leg on the un-quantised shadow)."""
@@ -419,8 +469,8 @@ class SpattenExtensions:
     def flush(self, layer: int):
         """Fold the last decode step's probabilities (still pending) into the accumulator."""
         st = self.layers[layer]
-        if self.cascade and st.pending_len > 0 and self.pq_local_v:
-            # the composed step: the final fp32 logits of the last step are in its planes' msb_logit, its (max, sum) in lse[0]
+        if self.cascade and st.pending_len > 0 and self.pq_logit_fold:
+            # the composed step / pq_cascade: the final fp32 logits of the last step are in its planes' msb_logit, its (max, sum) in lse[0]
             n = st.pending_len
             ops.importance_accumulate(st.acc, st.pq_planes.msb_logit[:, :, None, :n], st.lse[0][:, :, None, :])
             st.pending_len = 0

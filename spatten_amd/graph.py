@@ -206,7 +206,7 @@ class DecodeGraph:
                 synced.add(id(exts))
             st = exts.layers[layer]
             # (cascade importance swaps two stash buffers every step; the composed step over the quantised planes keeps one)
-            swap = exts.cascade and not exts.pq_local_v
+            swap = exts.cascade and not exts.pq_logit_fold
             cur = ((self.steps_traced - 1) & 1) if (swap and self.steps_traced > 0) else 0
             object.__setattr__(module, "attn_scores", st.stash[cur][:, :, None, :self.length_of(slab)])
 

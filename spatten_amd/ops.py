@@ -1429,7 +1429,7 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
                     head_ids: Optional[torch.Tensor] = None, head_abs: Optional[torch.Tensor] = None,
                     step: Optional["StepState"] = None, layout: int = 0, n_splits: int = 0, msb_only: bool = False,
                     workspace: Optional[DecodeWorkspace] = None, append=None, query_bits: Optional[int] = None,
-                    q_quant: Optional[tuple] = None, grouped: bool = False) -> torch.Tensor:
+                    q_quant: Optional[tuple] = None, grouped: bool = False, cascade=None) -> torch.Tensor:
     """Decode over the profiled planes (spatten_attn_decode_pq): MSB pass + LSB-only refetch for the flagged heads, P.V over
     the quantised values.  q [B,H,d]; returns out [B, H*d]; ``need_lsb`` int32 [B*H] is written.
     ``append`` = (k_new, v_new, k_cache | None, kr_cache, v_cache): the step's append INSIDE the MSB pass (round 5) — row kv_len - 1
@@ -1441,7 +1441,21 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
     ``grouped`` (needs ``query_bits``): the grouped-query form (spatten_attn_decode_pq_qint_gqa) — the MSB pass streams the planes
     once per KV head and scores the head's whole group on the int8 matrix cores; same results (q_int, q_scale, msb_logit and the
     MSB-only stash bit for bit, out / lse to rounding).  f16 / bf16, G = H / Hkv in [2, 32], head_dim 128, profile (8, 8); no
-    ``head_ids`` / ``head_abs``."""
+    ``head_ids`` / ``head_abs``.
+    ``cascade`` = (acc [H, >=kv_len] fp32, prev_lse [B,H,2] fp32, prev_len): the step with the cumulative token importance folded
+    into its launches (spatten_attn_decode_pq_cascade) — the previous step's probabilities (its logits in ``planes.msb_logit``, its
+    (max, sum) in ``prev_lse``, which this call refreshes) are added to acc for rows < prev_len (with ``step``: state word 3); out,
+    stash, lse and need_lsb are the plain step's bit for bit, and ``planes.msb_logit`` holds the logits the output came from
+    (flagged heads: the final ones).  ``lse`` is required; no ``append`` (call ``kv_append_planes`` first), no ``query_bits`` /
+    ``grouped``."""
+    if cascade is not None:
+        if query_bits is not None or grouped:
+            raise NotImplementedError("attn_decode_pqv(cascade=...) has no quantised-query / grouped form")
+        if append is not None:
+            raise NotImplementedError("attn_decode_pqv(cascade=...) does not append inside the launch: call "
+                                      "ops.kv_append_planes(...) first and pass append=None")
+        if lse is None:
+            raise ValueError("attn_decode_pqv(cascade=...) needs lse [B,H,2] fp32")
     if grouped and query_bits is None:
         raise ValueError("attn_decode_pqv(grouped=True) is a form of the quantised-query decode: pass query_bits (4..8)")
     if query_bits is not None:
@@ -1529,6 +1543,20 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
             _lib.check(_lib.load().spatten_attn_decode_pq_qint_gqa(ctypes.byref(qa), stream), "spatten_attn_decode_pq_qint_gqa")
             return out
         _lib.check(_lib.load().spatten_attn_decode_pq_qint(ctypes.byref(qa), stream), "spatten_attn_decode_pq_qint")
+        return out
+    if cascade is not None:
+        acc, prev_lse, prev_len = cascade
+        _dev(acc, prev_lse)
+        if acc.dtype != torch.float32 or acc.dim() != 2 or acc.stride(1) != 1 or acc.shape[0] != H or acc.shape[1] < kv_len \
+                or prev_lse.dtype != torch.float32 or prev_lse.numel() != B * H * 2 or not prev_lse.is_contiguous():
+            raise ValueError("cascade: acc [H, >=kv_len] fp32 with contiguous rows, prev_lse [B,H,2] fp32 contiguous")
+        if lse.dtype != torch.float32 or lse.numel() != B * H * 2 or not lse.is_contiguous():
+            raise ValueError("cascade: lse [B,H,2] fp32 contiguous")
+        ca = _lib.PQCascadeArgs()
+        ca.struct_size, ca.prev_len = ctypes.sizeof(_lib.PQCascadeArgs), int(prev_len)
+        ca.step = a
+        ca.importance_acc, ca.acc_sh, ca.prev_lse = acc.data_ptr(), acc.stride(0), prev_lse.data_ptr()
+        _lib.check(_lib.load().spatten_attn_decode_pq_cascade(ctypes.byref(ca), stream), "spatten_attn_decode_pq_cascade")
         return out
     _lib.check(_lib.load().spatten_attn_decode_pq(ctypes.byref(a), stream), "spatten_attn_decode_pq")
     return out
