@@ -1331,17 +1331,31 @@ class PQProfilePlanes:
     per-row scale, and the fp32 MSB-logit scratch [B, H, cap] the refetch pass reads.  Layouts are the library's (piece
     order); ``unpack`` undoes them for tests."""
 
-    def __init__(self, batch, kv_heads, heads, cap, d, device, key_bits: int = 4, value_bits: int = 8):
+    def __init__(self, batch, kv_heads, heads, cap, d, device, key_bits: int = 4, value_bits: int = 8, tensors=None):
+        """``tensors`` = (msb, lsb, scale, vq, vscale, msb_logit): preallocated planes of exactly these shapes — views into a
+        slab are accepted (rows contiguous at their pitch; the batch / head strides are passed on as they are)."""
         if (key_bits, value_bits) not in PQ_PROFILES:
             raise ValueError(f"unsupported bit profile {(key_bits, value_bits)}: one of {PQ_PROFILES}")
         self.key_bits, self.value_bits, self.d = int(key_bits), int(value_bits), d
         u8 = dict(dtype=torch.uint8, device=device)
-        self.msb = torch.zeros(batch, kv_heads, cap, d * key_bits // 8, **u8)
-        self.lsb = torch.zeros(batch, kv_heads, cap, d // 2, **u8)
-        self.scale = torch.ones(batch, kv_heads, cap, dtype=torch.float32, device=device)
-        self.vq = torch.zeros(batch, kv_heads, cap, d * value_bits // 8, **u8)
-        self.vscale = torch.ones(batch, kv_heads, cap, dtype=torch.float32, device=device)
-        self.msb_logit = torch.zeros(batch, heads, cap, dtype=torch.float32, device=device)
+        shapes = ((batch, kv_heads, cap, d * key_bits // 8), (batch, kv_heads, cap, d // 2), (batch, kv_heads, cap),
+                  (batch, kv_heads, cap, d * value_bits // 8), (batch, kv_heads, cap), (batch, heads, cap))
+        if tensors is None:
+            self.msb = torch.zeros(*shapes[0], **u8)
+            self.lsb = torch.zeros(*shapes[1], **u8)
+            self.scale = torch.ones(*shapes[2], dtype=torch.float32, device=device)
+            self.vq = torch.zeros(*shapes[3], **u8)
+            self.vscale = torch.ones(*shapes[4], dtype=torch.float32, device=device)
+            self.msb_logit = torch.zeros(*shapes[5], dtype=torch.float32, device=device)
+        else:
+            dts = (torch.uint8, torch.uint8, torch.float32, torch.uint8, torch.float32, torch.float32)
+            for t, shape, tdt in zip(tensors, shapes, dts):
+                if tuple(t.shape) != shape or t.dtype != tdt or t.stride(-1) != 1 or (t.dim() == 4 and t.stride(2) != shape[3]):
+                    raise ValueError(f"planes: expected {tdt} {shape} with contiguous rows, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+            if tensors[4].stride() != tensors[2].stride():
+                raise ValueError("planes: key and value scales share one pair of strides")
+            _dev(*tensors)
+            self.msb, self.lsb, self.scale, self.vq, self.vscale, self.msb_logit = tensors
         a = self.desc = _lib.PQPlanesDesc()
         a.struct_size = ctypes.sizeof(_lib.PQPlanesDesc)
         a.key_msb_bits, a.value_bits = self.key_bits, self.value_bits
