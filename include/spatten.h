@@ -195,11 +195,15 @@ size_t spatten_decode_qkv_exchange_bytes(int batch, int heads, int head_dim);
 int spatten_decode_set_team(int threads);
 int spatten_decode_qkv_supported(int dtype, int batch, int heads, int kv_heads, int head_dim, int kv_len_layout);
 /* Grouped-query models (heads > kv_heads; modify_llama.py:106-108 repeat_kv), round 6: the single-row step of bf16 / f16, head_dim
- * 128, without mask / head list / cascade accumulation / quantised keys streams a KV head's rows ONCE for its whole query group and
- * scores them on the matrix cores (csrc/decode_gqa.hip) instead of once per query head.  mode: -1 = where that form measured faster
+ * 128, without mask / head list / head importance / quantised keys / fused projections / flags streams a KV head's rows ONCE for
+ * its whole query group and scores them on the matrix cores (csrc/decode_gqa.hip) instead of once per query head.  The form serves
+ * the append, the stash, (max, sum), the device-length state and the fused cascade accumulation (importance_acc + prev_*: the
+ * previous stash rows come through LDS next to the keys; it adds what the per-query-head kernel adds, bit for bit; prev_scores must
+ * be 16-byte aligned with prev_sb / prev_sh multiples of 8 elements, or the step takes the per-query-head kernel).  mode: -1 = where that form measured faster
  * (the default: a cost model fitted to 27 measured shapes, csrc/decode_gqa.hip gqa_pays — 32 / 8 heads from ~3k rows, 64 / 8 from
  * ~1.5k; the layout length decides, so a static launch and the device-length form of one step take the same kernel), 0 = never, 1 = whenever the
- * step is eligible.  Process-wide; outputs of the two forms differ in summation order (low bits), both
+ * step is eligible.  Accumulation steps take the form in mode 1 ONLY: the default mode's rule was fitted to plain steps and no
+ * accumulation step has been timed in both forms yet (speed not measured).  Process-wide; outputs of the two forms differ in summation order (low bits), both
  * inside the stated tolerance.  Returns the previous mode + 1 (0..2), or SPATTEN_ERR_INVALID.  SPATTEN_DECODE_GQA in the
  * environment sets the initial mode. */
 int spatten_decode_set_gqa(int mode);
@@ -208,6 +212,11 @@ int spatten_decode_set_gqa(int mode);
  * mode, 0 otherwise (also for geometries the form does not serve).  No stream operation; the default mode's answer follows the
  * device's CU count. */
 int spatten_decode_gqa_selected(int dtype, int batch, int heads, int kv_heads, int head_dim, int kv_len_layout);
+/* 1 when spatten_attn_decode_args would launch THIS block in the matrix-core form under the current mode — the same eligibility
+ * routine the launch goes by: geometry, what the block carries (accumulation, mask, head list, ...), strides and alignments, the
+ * workspace — 0 otherwise, also for NULL, a wrong struct_size or a block the call would reject.  Host arithmetic only: no stream
+ * operation, nothing dereferenced beyond the block; answers on a machine without a GPU. */
+int spatten_decode_gqa_form(const spatten_decode_args_t* args);
 
 /* ------------------------------------------------------------------------------------------------
  * The chained decode launch (ABI 5, round 6): the attention step of ALL layers of one token — what the caller's per-layer

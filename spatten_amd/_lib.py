@@ -299,6 +299,8 @@ def _declare(lib):
     lib.spatten_decode_set_gqa.argtypes = [c_int]
     lib.spatten_decode_gqa_selected.restype = c_int
     lib.spatten_decode_gqa_selected.argtypes = [i, i, i, i, i, i]
+    lib.spatten_decode_gqa_form.restype = c_int
+    lib.spatten_decode_gqa_form.argtypes = [POINTER(DecodeArgs)]
     lib.spatten_prune_layer_cascade.restype = c_int
     lib.spatten_prune_layer_cascade.argtypes = [i, i, i, p, p, p, p, p, p, p, p, p, p, p, p, i, p, i, p, i64, p, p, i, i, i, i, p]
 def load():

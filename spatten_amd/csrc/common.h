@@ -470,6 +470,8 @@ int decode_rows(const DecodeCall& c, hipStream_t stream);
 // the grouped-query single-row step on the matrix cores (decode_gqa.hip): SPATTEN_OK after launching it, SPATTEN_ERR_UNSUPPORTED when
 // the launch is not one it serves (nothing launched; decode_rows then takes the per-query-head kernel)
 int decode_gqa_rows(const DecodeCall& c, hipStream_t stream);
+// ... and whether it would (the one eligibility routine both decode_gqa_rows and spatten_decode_gqa_form go by), with its split layout
+bool decode_gqa_plan(const DecodeCall& c, int& S, int& chunk32);
 // split-N factor of a decode launch over `units` softmax rows (decode_attn.hip); dense_rule = the 16-bit dense step's 8-split rule
 int decode_auto_splits(int units, int d, int kv_len, int elt, bool dense_rule);
 int decode_team();   // threads of the attention team of a single-shot decode step (decode_attn.hip: 512 or 256)

@@ -488,8 +488,9 @@ static int dispatch_decode(DecodeParams<T>& p, int d, int n_active, bool scores_
   }
 }
 
-// shared by the decode entry points and the small-q / fp32 leg of spatten_attn_prefill
-int decode_rows(const DecodeCall& c, hipStream_t stream) {
+// What decode_rows checks and lays out before it chooses a kernel (host arithmetic only: spatten_decode_gqa_form answers through it
+// too): SPATTEN_OK and the per-query-head launch shape, or the error the call returns.
+static int decode_rows_check(const DecodeCall& c, int& n_active, int& S, int& chunk, int& poll_merge) {
   const bool scores_only = (c.flags & SPATTEN_DECODE_SCORES_ONLY) != 0;
   const PQKeys* pq = c.pq;
   if ((!c.q && !c.qkv_x) || (!c.kr_cache && !pq) || !c.cos || !c.sin || (!scores_only && (!c.out || !c.v_cache))) return SPATTEN_ERR_INVALID;
@@ -497,7 +498,7 @@ int decode_rows(const DecodeCall& c, hipStream_t stream) {
                   c.k_new || c.n_q != 1 || !c.k_cache || pq || scores_only || c.batch != 1))
     return SPATTEN_ERR_INVALID;
   if (scores_only && (!c.scores || !c.lse || c.k_new)) return SPATTEN_ERR_INVALID;
-  int n_active = c.head_ids ? c.n_active : c.heads;
+  n_active = c.head_ids ? c.n_active : c.heads;
   if (n_active <= 0 || n_active > c.heads) return SPATTEN_ERR_INVALID;
   if (c.batch <= 0 || c.heads <= 0 || c.kv_heads <= 0 || c.heads % c.kv_heads != 0 || c.kv_len <= 0 || c.pos_q < 0 || c.n_q <= 0)
     return SPATTEN_ERR_INVALID;
@@ -521,18 +522,34 @@ int decode_rows(const DecodeCall& c, hipStream_t stream) {
   // the length the splits are laid out for: the step's own, or a common layout length of a whole turn (the device-length
   // form is laid out for its bound, kv_len)
   const int lay = (!c.step && c.layout_len > c.kv_len && c.n_q == 1) ? c.layout_len : c.kv_len;
-  int S = c.n_splits > 0 ? c.n_splits : decode_auto_splits(c.batch * n_active * c.n_q, c.head_dim, lay, c.dtype == SPATTEN_F32 ? 4 : 2, c.pq == nullptr);
+  S = c.n_splits > 0 ? c.n_splits : decode_auto_splits(c.batch * n_active * c.n_q, c.head_dim, lay, c.dtype == SPATTEN_F32 ? 4 : 2, c.pq == nullptr);
   if (S > lay) S = lay;
   if (S > kDecodeMaxSplits) S = kDecodeMaxSplits;
   // balanced chunks: ceil(N / S) rows per split (rounded up to the 8 rows of a stash line), whatever N is
-  const int chunk = ceil_div(ceil_div(lay, S), 8) * 8;
+  chunk = ceil_div(ceil_div(lay, S), 8) * 8;
   S = ceil_div(lay, chunk);
   if (S > 1 && (!c.workspace || (size_t)units > c.ws_units || S > ws_splits)) return SPATTEN_ERR_INVALID;
-  const size_t cnt_bytes = decode_cnt_bytes(c.ws_units);
   // single-hop merge (see the kernel): only when the grid cannot outnumber the workgroup slots of the chip.  Causal
   // multi-row launches are excluded (their later splits may be empty and return early... they still publish, but keep
   // the conservative protocol there).
-  const int poll_merge = (S > 1 && c.n_q == 1 && (long long)S * n_active * c.batch <= coresident_workgroups()) ? 1 : 0;
+  poll_merge = (S > 1 && c.n_q == 1 && (long long)S * n_active * c.batch <= coresident_workgroups()) ? 1 : 0;
+  if (c.proj_w != nullptr && (!c.proj_out || c.proj_n <= 0 || c.n_q != 1 || scores_only || c.proj_w_sn < (int64_t)c.heads * c.head_dim))
+    return SPATTEN_ERR_INVALID;
+  return SPATTEN_OK;
+}
+
+// shared by the decode entry points and the small-q / fp32 leg of spatten_attn_prefill
+int decode_rows(const DecodeCall& c, hipStream_t stream) {
+  const bool scores_only = (c.flags & SPATTEN_DECODE_SCORES_ONLY) != 0;
+  const PQKeys* pq = c.pq;
+  int n_active, S, chunk, poll_merge;
+  {
+    const int rc_c = decode_rows_check(c, n_active, S, chunk, poll_merge);
+    if (rc_c != SPATTEN_OK) return rc_c;
+  }
+  const int units = c.batch * c.heads * c.n_q;          // workspace is indexed by the FULL head id
+  const int ws_splits = c.ws_splits > 0 ? c.ws_splits : kDecodeMaxSplits;
+  const size_t cnt_bytes = decode_cnt_bytes(c.ws_units);
 
   // ---- the output projection of the step (modify_llama.py:163) as a second launch of the same call: one C call per
   // layer-step for the host.  (r03: fusing it INTO the launch — projection waves in the decode workgroups that stream the
@@ -541,8 +558,6 @@ int decode_rows(const DecodeCall& c, hipStream_t stream) {
   // hand-off "all heads merged -> every CU" costs a poll round trip plus an activation read under load, more than the
   // kernel boundary it replaces.  HISTORY.md, r04 §3.9.)
   const bool want_proj = c.proj_w != nullptr;
-  if (want_proj && (!c.proj_out || c.proj_n <= 0 || c.n_q != 1 || scores_only || c.proj_w_sn < (int64_t)c.heads * c.head_dim))
-    return SPATTEN_ERR_INVALID;
   // grouped-query step on the matrix cores (decode_gqa.hip, round 6): a kv head's rows streamed once for its whole query group
   {
     const int rc_g = decode_gqa_rows(c, stream);
@@ -659,9 +674,9 @@ extern "C" int spatten_decode_workspace_status(void* workspace, void* stream) {
   return SPATTEN_ERR_TIMEOUT;
 }
 
-extern "C" int spatten_attn_decode_args(const spatten_decode_args_t* a, void* stream) {
+// the argument block as a DecodeCall (`keys`: storage for the quantised-key description the call may point at)
+static int decode_call_of(const spatten_decode_args_t* a, DecodeCall& c, PQKeys& keys) {
   if (!a || a->struct_size != sizeof(spatten_decode_args_t)) return SPATTEN_ERR_INVALID;
-  DecodeCall c;
   c.dtype = a->dtype;
   c.q = a->q; c.q_sb = a->q_sb; c.q_sh = a->q_sh;
   c.k_cache = a->k_cache; c.kr_cache = a->kr_cache; c.v_cache = a->v_cache; c.kv_sb = a->kv_sb; c.kv_sh = a->kv_sh;
@@ -685,7 +700,6 @@ extern "C" int spatten_attn_decode_args(const spatten_decode_args_t* a, void* st
   c.proj_out_sb = a->proj_out_sb; c.proj_n = a->proj_n;
   c.qkv_x = a->qkv_x; c.qkv_w = a->qkv_weight; c.qkv_w_sn = a->qkv_w_sn; c.qkv_bias = a->qkv_bias; c.qkv_xch = a->qkv_exchange;
   c.qkv_hidden = a->qkv_hidden;
-  PQKeys keys;
   if (a->pq_msb) {
     if (!a->pq_lsb || !a->pq_scale || !a->pq_need_lsb) return SPATTEN_ERR_INVALID;
     if (a->head_dim != 64 && a->head_dim != 128) return SPATTEN_ERR_UNSUPPORTED;
@@ -694,7 +708,22 @@ extern "C" int spatten_attn_decode_args(const spatten_decode_args_t* a, void* st
     keys.threshold = a->pq_threshold; keys.need = a->pq_need_lsb;
     c.pq = &keys;
   }
-  return decode_rows(c, (hipStream_t)stream);
+  return SPATTEN_OK;
+}
+
+extern "C" int spatten_attn_decode_args(const spatten_decode_args_t* a, void* stream) {
+  DecodeCall c;
+  PQKeys keys;
+  const int rc = decode_call_of(a, c, keys);
+  return rc != SPATTEN_OK ? rc : decode_rows(c, (hipStream_t)stream);
+}
+
+extern "C" int spatten_decode_gqa_form(const spatten_decode_args_t* a) {
+  DecodeCall c;
+  PQKeys keys;
+  int n_active, S, chunk, poll_merge;
+  if (decode_call_of(a, c, keys) != SPATTEN_OK || decode_rows_check(c, n_active, S, chunk, poll_merge) != SPATTEN_OK) return 0;
+  return decode_gqa_plan(c, S, chunk) ? 1 : 0;
 }
 
 extern "C" int spatten_attn_decode(int dtype, const void* q, int64_t q_sb, int64_t q_sh, void* k_cache,

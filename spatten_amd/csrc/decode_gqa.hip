@@ -55,6 +55,9 @@ struct GqaParams {
   unsigned* ws_err; unsigned* ws_cnt; unsigned long long* ws_part; int64_t ws_unit;
   int B, H, Hkv, G, N, S, chunk, poll_merge;
   float sqrt_d;
+  // CASC (cascade importance, deferred by one step: decode_body.h): the previous step's stash + (max, sum) folded into acc [H, >= N]
+  // (behind the plain step's arguments: their offsets are those of the instantiations without the fold)
+  const T* prev_scores; int64_t pv_sb, pv_sh; float* prev_lse; float* acc; int64_t acc_sh; int prev_len;
 };
 
 // s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt in bits 3:0 and 15:14; expcnt / lgkmcnt left at "no wait")
@@ -63,12 +66,22 @@ template <int N> __device__ inline void wait_vm() {
   __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
 }
 
-template <typename T, bool DYN>
+// CASC: the fused cascade accumulation of decode_body.h on this mapping.  A ring stage gets a third part, the PREVIOUS step's stash
+// rows of the tile's 32 keys for the group's (up to 32) heads — [head][32 keys] x 2 bytes = 2 KiB, 144 KiB of LDS per workgroup
+// (of 160) — fetched by NP = 2 more LDS-DMA requests per tile, issued IN FRONT of the tile's value half (so a tile's requests are
+// K x NK | P x NP, V x NK): "the values have landed" then proves the previous rows have, and the lane that owns stash entry
+// (head col < G, key) reads its 16 entries from LDS and adds exp(prev - m) / l to acc[head, key], one atomicAdd per (b, h, key)
+// with key < prev_len — the per-query-head kernel's expression, term for term.  The vmcnt waits below grow by exactly the added
+// requests.  The (max, sum) rows and the keys of the 16-byte piece that the previous rows' bound cuts (LDS-DMA moves whole pieces;
+// nothing is read past the bound) are ordinary loads issued in front of the first tile.
+template <typename T, bool DYN, bool CASC = false>
 __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p) {
   constexpr int D = 128, KK = D / 16, DB = D / 32, KT = 32, NW = 4;
   constexpr int KBYTES = KT * D * 2;                  // a tile's key rows (8 KiB); as many value rows
-  constexpr int STAGE = 2 * KBYTES, WBUF = 2 * STAGE; // a wave's ring: two stages of { K, V }
+  constexpr int PBYTES = CASC ? 32 * KT * 2 : 0;      // CASC: the previous stash rows of a tile, [32 heads][32 keys]
+  constexpr int STAGE = 2 * KBYTES + PBYTES, WBUF = 2 * STAGE; // a wave's ring: two stages of { K, V (, P) }
   constexpr int NK = KBYTES / 1024;                   // DMA instructions per tile and operand
+  constexpr int NP = PBYTES / 1024;                   // ... and for the previous stash rows
   constexpr int PITCH = D + 4;                        // floats per (wave, column) partial in LDS: o[D], m, l
   using frag = typename Mfma<T>::frag;
   using V8 = Vec8<T>;
@@ -88,6 +101,8 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
 
   int n_live = p.N;
   if (DYN) n_live = p.step[0];                        // (a scalar load: waited for behind the first tile's requests)
+  int cnt_dyn = 0, pl_dyn = 0;
+  if (CASC && DYN) { cnt_dyn = p.step[2]; pl_dyn = p.step[3]; }   // the state's step count (buffer parity) and previous length
 
   const T* krb = p.krc + b * p.kv_sb + hkv * p.kv_sh;
   const T* vb = p.vc + b * p.kv_sb + hkv * p.kv_sh;
@@ -119,7 +134,38 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
 #pragma unroll
     for (int i = 0; i < NK; ++i) dma16a(k_rsrc, ka + i * 1024, kbase ^ (((i * 4) & 15) << 4), soff + i * 1024);
   };
+  // CASC: request r of a tile's previous rows: lane -> head 16 r + (lane >> 2), physical 16-byte slot lane & 3 of the head's 64
+  // bytes, which holds keys [8 lp, +8) with lp = slot ^ ((head >> 2) & 3) (heads 4 apart share LDS banks).  The row offset is part
+  // of the LANE's offset, so the descriptor's bound covers it; a lane whose piece is not wholly below the bound, or whose head is
+  // not one of the group's, asks for an offset past the bound: nothing is read.
+  const int p_clamp = !CASC ? 0 : DYN ? p.N : p.prev_len;      // rows [0, p_clamp) of a previous stash row exist
+  const int p_c8 = p_clamp & ~7;
+  constexpr int kPastBound = 0x7FFFFFF0;
+  i32x4 p_rsrc = k_rsrc;
+  int p_voff[NP > 0 ? NP : 1], p_lp8 = 0;
+  if (CASC) {
+#pragma unroll
+    for (int r = 0; r < NP; ++r) {
+      const int head = 16 * r + (lane >> 2);
+      const int lp = (lane & 3) ^ ((head >> 2) & 3);           // (head >> 2) & 3 = (lane >> 4) & 3 for both r
+      p_lp8 = 8 * lp;
+      p_voff[r] = head < G ? (int)(head * p.pv_sh * 2) + 16 * lp : -1;
+    }
+  }
+  auto prev_rsrc_of = [&](const T* base) {
+    const uint64_t a = (uint64_t)(base + b * p.pv_sb + (int64_t)(hkv * G) * p.pv_sh);
+    return i32x4{(int)__builtin_amdgcn_readfirstlane((uint32_t)a), (int)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32) & 0xFFFFu),
+                 (int)((G - 1) * p.pv_sh * 2 + (int64_t)p_c8 * 2), 0x00020000};
+  };
+  auto dma_prev = [&](int tile, int stage) {
+    const int row0 = lo + tile * KT;
+    const bool whole = row0 + p_lp8 + 8 <= p_c8;
+    const unsigned pa = lds_wbuf + stage * STAGE + 2 * KBYTES;
+#pragma unroll
+    for (int r = 0; r < NP; ++r) dma16a(p_rsrc, pa + r * 1024, (whole && p_voff[r] >= 0) ? p_voff[r] + row0 * 2 : kPastBound, 0);
+  };
   auto dma_values = [&](int tile, int stage) {
+    if (CASC) dma_prev(tile, stage);
     const int ln = opaque_lane(lane);
     const int lr = ln >> 4, ps = ln & 15;
     const int vbase = lr * 256 + ((ps ^ (4 * lr)) << 4);
@@ -132,6 +178,25 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   // ---- the group's queries as B operands: column g = head hkv G + g, fragment kk holds elements [16 kk + 8 hi, +8), so kk and
   // kk + KK/2 are the (x[i], x[i + d/2]) pairs RoPE combines.  Columns >= G: zeros.  Their rows are requested FIRST (a wave's loads
   // return in order: behind the tile the rotation would wait for the tile), then the first tile, then the rotation.
+  // CASC: the previous step's (max, sum) of the lane's head and the lane's four keys [p_c8 + 4 hi, +4) of the piece the bound cuts;
+  // DYN: of both buffers (the step count decides which of the two is "previous") — requested in front of everything else
+  float ml_a[2] = {0.f, 1.f}, ml_b[2] = {0.f, 1.f};
+  T tail_a[4], tail_b[4];
+  if (CASC) {
+    const int gq = min(col, G - 1);
+    const float* ml = p.prev_lse + 2 * (b * p.H + hkv * G + gq);
+    ml_a[0] = ml[0]; ml_a[1] = ml[1];
+    const T* pr = p.prev_scores + b * p.pv_sb + (int64_t)(hkv * G + gq) * p.pv_sh;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tail_a[e] = pr[max(min(p_c8 + 4 * hi + e, p_clamp - 1), 0)];
+    if (DYN) {
+      const float* m2 = p.lse + 2 * (b * p.H + hkv * G + gq);
+      ml_b[0] = m2[0]; ml_b[1] = m2[1];
+      const T* pr2 = p.scores + b * p.sc_sb + (int64_t)(hkv * G + gq) * p.sc_sh;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tail_b[e] = pr2[max(min(p_c8 + 4 * hi + e, p_clamp - 1), 0)];
+    }
+  }
   raw_t q_raw[KK / 2][4];
   {
     const int gq = min(col, G - 1);
@@ -153,7 +218,20 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   __builtin_amdgcn_sched_barrier(0);
   // the first tile goes out before anything is waited for (laid out for the bound: a device-length step may find it past its length)
   const int nt_bound = (min(lo + p.chunk, p.N) - lo + KT - 1) / KT;
-  if (wave < nt_bound) dma_tile(wave, 0);
+  // CASC && DYN: which buffer holds the previous rows is known once the state's step count is back: step k (1-based) writes
+  // buffer (k - 1) & 1 and folds the other one (decode_body.h) — the first tile's keys are in flight while that is waited for
+  bool odd = false;
+  if (CASC && DYN) {
+    if (wave < nt_bound) dma_keys(wave, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    odd = ((__builtin_amdgcn_readfirstlane(cnt_dyn) - 1) & 1) != 0;
+    p_rsrc = prev_rsrc_of(odd ? p.scores : p.prev_scores);
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave < nt_bound) dma_values(wave, 0);
+  } else {
+    if (CASC) p_rsrc = prev_rsrc_of(p.prev_scores);
+    if (wave < nt_bound) dma_tile(wave, 0);
+  }
   if (wave + NW < nt_bound) dma_tile(wave + NW, 1);
   SPATTEN_GSTAMP(1);          // two tiles requested
   __builtin_amdgcn_sched_barrier(0);
@@ -195,6 +273,23 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
 
   const float rsqrt_d = 1.0f / p.sqrt_d;
   T* stashp = (p.scores != nullptr && col < G) ? p.scores + b * p.sc_sb + (int64_t)(hkv * G + col) * p.sc_sh : nullptr;
+  float* lse_cur = p.lse;
+  const int prev_len = !CASC ? 0 : DYN ? __builtin_amdgcn_readfirstlane(pl_dyn) : p.prev_len;
+  float casc_m = 0.f, casc_rl = 0.f;
+  T tail[4];
+  float* accp = nullptr;
+  if (CASC) {
+    if (DYN && odd) {                                 // the writing side follows the parity too
+      if (col < G) stashp = const_cast<T*>(p.prev_scores) + b * p.pv_sb + (int64_t)(hkv * G + col) * p.pv_sh;
+      lse_cur = p.prev_lse;
+    }
+    const float pm = odd ? ml_b[0] : ml_a[0], pl = odd ? ml_b[1] : ml_a[1];
+    casc_m = (pm == -INFINITY) ? 0.f : pm;
+    casc_rl = 1.0f / pl;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tail[e] = (DYN && odd) ? tail_b[e] : tail_a[e];
+    accp = p.acc + (int64_t)(hkv * G + min(col, G - 1)) * p.acc_sh;
+  }
   float m_run = -INFINITY, l_run = 0.f;
   f32x16 o[DB];
 #pragma unroll
@@ -213,7 +308,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     // loads return in order: "at most X outstanding" with X = the requests issued behind the wanted ones proves those have landed
     // whatever the stash stores in between do (they may only make the wait longer)
     if (edge) {
-      if (more) wait_vm<2 * NK>(); else wait_vm<0>();
+      if (more) wait_vm<2 * NK + NP>(); else wait_vm<0>();        // (behind this tile's V: K, P, V of the next one)
       // value rows the cache does not hold: zero (their P is 0, but 0 x stale bits may be NaN); then the new token's rows
       char* va = wbuf + stage * STAGE + KBYTES;
 #pragma unroll
@@ -250,7 +345,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
         }
       }
     } else {
-      if (more) wait_vm<3 * NK>(); else wait_vm<NK>();            // the tile's key rows have landed
+      if (more) wait_vm<3 * NK + 2 * NP>(); else wait_vm<NK + NP>();   // the tile's key rows have landed (behind them: this tile's P, V; K, P, V of the next)
     }
     __builtin_amdgcn_sched_barrier(0);
     if (k == 0) SPATTEN_GSTAMP(3);   // first tile's keys landed
@@ -367,9 +462,29 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     SPATTEN_GSTAMP_IT(k, 3);
     // ---- O^T += Vt · P^T: the tile's value rows have landed ------------------------------------------------------------------------
     __builtin_amdgcn_sched_barrier(0);
-    if (!edge) { if (more2) wait_vm<3 * NK>(); else if (more) wait_vm<2 * NK>(); else wait_vm<0>(); }   // (behind V: K, V of the next tile, K of the one after)
+    if (!edge) { if (more2) wait_vm<3 * NK + NP>(); else if (more) wait_vm<2 * NK + NP>(); else wait_vm<0>(); }   // (behind V: K, P, V of the next tile, K of the one after)
     __builtin_amdgcn_sched_barrier(0);
     SPATTEN_GSTAMP_IT(k, 4);
+    if (CASC) {
+      // the previous step's probability of the lane's 16 keys (their rows came in front of the values: landed): register group q4
+      // = keys row0 + 8 q4 + 4 hi + 0..3 = half `hi` of logical piece q4 of the head's 64 bytes.  (The atomics are requests of the
+      // wave like the stash stores: they may only make a later wait longer.)
+      if (col < G && row0 < prev_len) {
+        const char* pa = wbuf + stage * STAGE + 2 * KBYTES + col * 64 + hi * 8;
+        const int sw = (col >> 2) & 3;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          typedef T t4 __attribute__((ext_vector_type(4)));
+          const t4 pv = *reinterpret_cast<const t4*>(pa + ((q4 ^ sw) << 4));
+          const int key = row0 + 8 * q4 + 4 * hi;
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (key + e < prev_len && key + e < N)
+              atomicAdd(accp + key + e, __expf(DT<T>::to_f32(key >= p_c8 ? tail[e] : (T)pv[e]) - casc_m) * casc_rl);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     {
       // lane (col, hi) needs, for d = 32 db + col, the 8 keys its P fragment holds — elements 0..3: keys 16 t + 4 hi + 0..3,
       // elements 4..7: 16 t + 8 + 4 hi + 0..3 — two transposing reads 8 rows apart (prefill_attn.hip, the VTR form)
@@ -438,7 +553,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     const int unit = unit0 + g;
     if (p.S == 1) {
       p.out[b * p.out_sb + (int64_t)(hkv * G + g) * D + e] = DT<T>::from_f32(o_tot / l_tot);
-      if (p.lse != nullptr && e == 0) { p.lse[2 * unit] = mwg; p.lse[2 * unit + 1] = l_tot; }
+      if (lse_cur != nullptr && e == 0) { lse_cur[2 * unit] = mwg; lse_cur[2 * unit + 1] = l_tot; }
       continue;
     }
     unsigned long long* part = p.ws_part + (int64_t)unit * p.ws_unit + (int64_t)split * (D + 2);
@@ -529,7 +644,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
       lg = fmaf(fold[3 * e + 2], w1, lg * w0);
       p.out[b * p.out_sb + (int64_t)(hkv * G + g) * D + e] = DT<T>::from_f32(og / lg);
       if (e == 0) {
-        if (p.lse != nullptr) { p.lse[2 * unit] = mn; p.lse[2 * unit + 1] = lg; }
+        if (lse_cur != nullptr) { lse_cur[2 * unit] = mn; lse_cur[2 * unit + 1] = lg; }
         p.ws_cnt[2 * unit + 1] = gen + 1u;            // next launch: new tag
       }
     }
@@ -574,29 +689,56 @@ static inline void gqa_layout(int cols, int lay, int n_splits, int ws_splits, in
   S = (lay + chunk32 - 1) / chunk32;
 }
 
-// The grouped-query step on the matrix cores, when the launch is one this kernel serves: SPATTEN_OK after launching,
-// SPATTEN_ERR_UNSUPPORTED (nothing launched: the caller takes the per-query-head kernel) otherwise.
-int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
+// Is this (validated: decode_rows) launch one the matrix-core form serves under the current mode, and with which split layout?  The ONE
+// eligibility routine: decode_gqa_rows launches by it and spatten_decode_gqa_form answers by it.  Host arithmetic only.
+// Served: the single-row step of a grouped-query model (16-bit, d = 128, G <= 32), with or without append, stash, (max, sum),
+// device-length state and the fused cascade accumulation (importance_acc + prev_*).  Not served: mask, head list, head
+// importance, quantised keys, fused projections, flags.
+bool decode_gqa_plan(const DecodeCall& c, int& S, int& chunk32) {
   const int mode = gqa_mode();
-  if (mode == 0 || c.heads == c.kv_heads || c.head_dim != 128 || (c.dtype != SPATTEN_BF16 && c.dtype != SPATTEN_F16)) return SPATTEN_ERR_UNSUPPORTED;
-  if (c.n_q != 1 || c.mask || c.pq || c.acc || c.prev_scores || c.qkv_x || c.head_ids || c.head_abs || c.flags != 0 || c.causal ||
+  if (mode == 0 || c.heads == c.kv_heads || c.head_dim != 128 || (c.dtype != SPATTEN_BF16 && c.dtype != SPATTEN_F16)) return false;
+  if (c.n_q != 1 || c.mask || c.pq || c.qkv_x || c.head_ids || c.head_abs || c.flags != 0 || c.causal ||
       !c.q || !c.kr_cache || !c.v_cache || !c.out)
-    return SPATTEN_ERR_UNSUPPORTED;
+    return false;
+  if (c.kv_heads <= 0 || c.heads % c.kv_heads != 0) return false;
   const int G = c.heads / c.kv_heads;
-  if (G > 32 || c.lse_q > 1) return SPATTEN_ERR_UNSUPPORTED;
+  if (G > 32 || c.lse_q > 1) return false;
+  if (!c.acc && c.prev_scores) return false;
+  if (c.acc) {
+    // the previous stash rows come by 16-byte LDS-DMA pieces through a 32-bit descriptor over the group's rows; a layout that does
+    // not fit takes the per-query-head kernel.  Default mode: no accumulation step has measured faster in this form yet (DESIGN.md
+    // 3.1c) — mode 1 only.
+    if (mode < 0) return false;
+    if (!c.prev_scores || !c.prev_lse || c.prev_len < 0 || (!c.step && c.prev_len > c.kv_len)) return false;
+    if ((uintptr_t)c.prev_scores % 16 != 0 || c.pv_sb % 8 != 0 || c.pv_sh % 8 != 0 || c.pv_sh < 0) return false;
+    if ((int64_t)(G - 1) * c.pv_sh * 2 + (int64_t)c.kv_len * 2 >= 0x7FFFFFF0ll) return false;
+    if (c.step && (!c.scores || !c.lse || (uintptr_t)c.scores % 16 != 0 || c.sc_sb != c.pv_sb || c.sc_sh != c.pv_sh)) return false;
+  }
   // the split layout follows the LAYOUT length (a static launch laid out for a longer cache: the decomposition — and with it
   // every bit of `out` — of the device-length form whose bound is that length); so does the choice of the kernel, or a static
   // launch and the device-length form of the same step could take different kernels around the threshold
   const int lay = (!c.step && c.layout_len > c.kv_len) ? c.layout_len : c.kv_len;
-  if ((int64_t)c.kv_len * 256 >= 0x7FFFFFFFll) return SPATTEN_ERR_UNSUPPORTED;          // 32-bit byte offsets inside a plane
-  if ((c.kv_sb | c.kv_sh) % 8 != 0 || (c.q_sb | c.q_sh) % 8 != 0 || (c.k_new && (c.new_sb | c.new_sh) % 8 != 0)) return SPATTEN_ERR_UNSUPPORTED;
+  if ((int64_t)c.kv_len * 256 >= 0x7FFFFFFFll) return false;          // 32-bit byte offsets inside a plane
+  if ((c.kv_sb | c.kv_sh) % 8 != 0 || (c.q_sb | c.q_sh) % 8 != 0 || (c.k_new && (c.new_sb | c.new_sh) % 8 != 0)) return false;
   const int units = c.batch * c.heads;
   const int ws_splits = c.ws_splits > 0 ? c.ws_splits : kDecodeMaxSplits;
   const int cols = c.batch * c.kv_heads;
-  int S, chunk32;
   gqa_layout(cols, lay, c.n_splits, ws_splits, S, chunk32);
-  if (mode < 0 && !gqa_pays(c.batch, c.heads, c.kv_heads, lay, chunk32)) return SPATTEN_ERR_UNSUPPORTED;
-  if (S > 1 && (!c.workspace || (size_t)units > c.ws_units)) return SPATTEN_ERR_UNSUPPORTED;
+  if (mode < 0 && !gqa_pays(c.batch, c.heads, c.kv_heads, lay, chunk32)) return false;
+  if (S > 1 && (!c.workspace || (size_t)units > c.ws_units)) return false;
+  return true;
+}
+
+// The grouped-query step on the matrix cores, when the launch is one this kernel serves: SPATTEN_OK after launching,
+// SPATTEN_ERR_UNSUPPORTED (nothing launched: the caller takes the per-query-head kernel) otherwise.
+int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
+  int S, chunk32;
+  if (!decode_gqa_plan(c, S, chunk32)) return SPATTEN_ERR_UNSUPPORTED;
+  const int G = c.heads / c.kv_heads;
+  const int ws_splits = c.ws_splits > 0 ? c.ws_splits : kDecodeMaxSplits;
+  const int cols = c.batch * c.kv_heads;
+  // (a static step with nothing to fold — prev_len = 0 — is the plain step: no previous row need exist)
+  const bool casc = c.acc != nullptr && (c.step != nullptr || c.prev_len > 0);
   const int poll_merge = (S > 1 && (long long)S * cols <= coresident_workgroups()) ? 1 : 0;
   const size_t cnt_bytes = decode_cnt_bytes(c.ws_units);
 
@@ -619,6 +761,8 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   p.sc_vec = (c.scores && ((uintptr_t)c.scores % 8 == 0) && c.sc_sb % 4 == 0 && c.sc_sh % 4 == 0) ? 1 : 0;      \
   if (p.sc_vec && (uintptr_t)c.scores % 16 == 0 && c.sc_sb % 8 == 0 && c.sc_sh % 8 == 0 && sizeof(T) == 2) p.sc_vec = 2; \
   p.lse = c.lse;                                                                                                 \
+  p.prev_scores = (const T*)c.prev_scores; p.pv_sb = c.pv_sb; p.pv_sh = c.pv_sh; p.prev_lse = (float*)c.prev_lse;  \
+  p.acc = c.acc; p.acc_sh = c.acc_sh; p.prev_len = c.prev_len;                                                   \
   p.ws_err = (unsigned*)c.workspace;                                                                             \
   p.ws_cnt = c.workspace ? (unsigned*)((char*)c.workspace + kDecodeWsHeader) : nullptr;                          \
   p.ws_part = c.workspace ? (unsigned long long*)((char*)c.workspace + kDecodeWsHeader + cnt_bytes) : nullptr;   \
@@ -626,7 +770,10 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   p.B = c.batch; p.H = c.heads; p.Hkv = c.kv_heads; p.G = G; p.N = c.kv_len; p.S = S; p.chunk = chunk32;         \
   p.poll_merge = poll_merge; p.sqrt_d = sqrtf((float)c.head_dim);                                                \
   const dim3 grid(S, c.kv_heads, c.batch);                                                                       \
-  if (c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true>), grid, dim3(256), 0, stream, p);                   \
+  if (casc) {                                                                                                    \
+    if (c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true, true>), grid, dim3(256), 0, stream, p);           \
+    else hipLaunchKernelGGL((decode_gqa_kernel<T, false, true>), grid, dim3(256), 0, stream, p);                 \
+  } else if (c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true>), grid, dim3(256), 0, stream, p);            \
   else hipLaunchKernelGGL((decode_gqa_kernel<T, false>), grid, dim3(256), 0, stream, p);                         \
   return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
 

@@ -164,7 +164,7 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
                 head_ids: Optional[torch.Tensor] = None, scores_only: bool = False,
                 cascade: Optional[tuple] = None, pq: Optional[tuple] = None,
                 head_abs: Optional[torch.Tensor] = None, step: Optional["StepState"] = None,
-                layout: int = 0, proj: Optional[tuple] = None) -> torch.Tensor:
+                layout: int = 0, proj: Optional[tuple] = None, gqa_form: bool = False) -> torch.Tensor:
     """Fused decode attention (modify_llama.py:86-147 at q_len=1).
 
     q [B,H,d]; k_cache (un-rotated, only appended to) / kr_cache (rotated shadow, see build_shadow) /
@@ -185,6 +185,8 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     [length, bound) of kr_cache / v_cache must hold finite values.
     proj = (weight [N, H*d], bias [N] or None, proj_out [B, N]): the step's output projection (modify_llama.py:163) issued by
     the same C call (a second launch of spatten_gemv's kernel: one host call per layer-step); ``proj_out`` is filled.
+    gqa_form: build the argument block, launch NOTHING and return whether the call would run in the matrix-core grouped-query
+    form under the current mode (spatten_decode_gqa_form; see decode_gqa_form).
     Returns out [B, H*d]."""
     _dev(q, k_cache, kr_cache, v_cache, cos, sin, k_new, v_new, mask, out, scores, lse, position_ids, head_abs)
     if position_ids is not None and position_ids.dtype != torch.int64:
@@ -267,6 +269,8 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
         a.pq_pl_sb, a.pq_pl_sh = planes.msb.stride(0), planes.msb.stride(1)
         a.pq_sc_sb, a.pq_sc_sh = planes.scale.stride(0), planes.scale.stride(1)
         a.pq_threshold, a.pq_need_lsb = float(threshold), need_lsb.data_ptr()
+    if gqa_form:
+        return bool(lib.spatten_decode_gqa_form(ctypes.byref(a)))
     _lib.check(lib.spatten_attn_decode_args(ctypes.byref(a), stream), "spatten_attn_decode")
     return out
 
@@ -651,6 +655,13 @@ def decode_gqa_selected(dtype: torch.dtype, batch: int, heads: int, kv_heads: in
     """Would a plain single-row step of this geometry run in the matrix-core grouped-query form under the current mode
     (spatten_decode_gqa_selected)?  `kv_len_layout`: the cache length of a static launch / the bound of the device-length form."""
     return bool(_lib.load().spatten_decode_gqa_selected(_DT.get(dtype, -1), int(batch), int(heads), int(kv_heads), int(head_dim), int(kv_len_layout)))
+
+
+def decode_gqa_form(*args, **kwargs) -> bool:
+    """Would ``attn_decode(*args, **kwargs)`` — this very call: its tensors, strides, cascade / mask / head list, splits — run in the
+    matrix-core grouped-query form under the current mode (spatten_decode_gqa_form)?  The argument block is assembled exactly as
+    for the launch; nothing is launched."""
+    return attn_decode(*args, gqa_form=True, **kwargs)
 
 
 def gemv(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
