@@ -119,6 +119,11 @@ int spatten_attn_decode(int dtype,
  *                              DEVICE memory, NULL = all); rows of pruned heads in out / scores / lse are left untouched
  *   flags                      SPATTEN_DECODE_SCORES_ONLY: write the stash and lse only (no V traffic, no output) —
  *                              pass 1 of local V pruning (scores, lse required; k_new must be NULL)
+ *                              SPATTEN_DECODE_GROUPED_HEADS: opt-in — a single-row step of a grouped-query model that carries
+ *                              head_ids / n_active_heads and / or head_abs_acc may take the matrix-core grouped form
+ *                              (spatten_decode_set_gqa below, mode 1 only).  Nothing else about the step changes; without a
+ *                              head list and head importance the bit changes nothing; with SCORES_ONLY the step stays on
+ *                              the per-query-head kernel.  Other bits are ignored.
  *   importance_acc ...         cascade (cumulative) importance, README.md:11, fused and deferred by one step: while this
  *                              step's keys stream, acc[h, j] += exp(prev_scores[b,h,j] - prev_lse[b,h,0]) / prev_lse[b,h,1]
  *                              for j < prev_len — the softmax probabilities of the PREVIOUS decode step, whose stash and
@@ -136,6 +141,7 @@ int spatten_attn_decode(int dtype,
  *                              must be NULL / 0 in this mode (append with spatten_kv_append + spatten_pq_pack first);
  *                              `scores` then holds the logits of the quantised keys that the output was computed from. */
 #define SPATTEN_DECODE_SCORES_ONLY 1
+#define SPATTEN_DECODE_GROUPED_HEADS 2
 typedef struct spatten_decode_args {
   uint32_t struct_size;            /* sizeof(spatten_decode_args_t) of the caller */
   int32_t dtype;
@@ -205,7 +211,14 @@ int spatten_decode_qkv_supported(int dtype, int batch, int heads, int kv_heads, 
  * step is eligible.  Accumulation steps take the form in mode 1 ONLY: the default mode's rule was fitted to plain steps and no
  * accumulation step has been timed in both forms yet (speed not measured).  Process-wide; outputs of the two forms differ in summation order (low bits), both
  * inside the stated tolerance.  Returns the previous mode + 1 (0..2), or SPATTEN_ERR_INVALID.  SPATTEN_DECODE_GQA in the
- * environment sets the initial mode. */
+ * environment sets the initial mode.
+ * Head pruning (head_ids / n_active_heads, head_abs_acc) takes the form only when the block sets SPATTEN_DECODE_GROUPED_HEADS in
+ * its flags, and in mode 1 ONLY (opt-in, correct, speed not measured, no automatic selection).  The grid is still one workgroup
+ * column per KV head: each workgroup reads the device list, a pruned head costs nothing, and a group without a survivor streams
+ * and appends nothing (as in the per-query-head form, where only launched heads append).  Rows of pruned heads in out / scores /
+ * lse / importance_acc / head_abs_acc are left untouched; live heads carry the bits of the plain grouped step.  head_abs_acc is
+ * added in a fixed order (run-to-run identical) that differs from the per-query-head kernel's: the two forms agree to fp32
+ * rounding there, not bit for bit. */
 int spatten_decode_set_gqa(int mode);
 /* 1 when a plain single-row step of this geometry (dtype bf16 / f16, head_dim 128, heads > kv_heads, kv_len_layout = the layout length:
  * the cache length of a static launch, the bound of the device-length form) is launched in the matrix-core form under the current

@@ -20,6 +20,19 @@
 // the tile loop has no special row.  Logits carry both reference roundings (:111-113); the stash holds them pre-mask (:116-119).
 // Split partials ({value, tag} granules) and the merge are the decode family's (decode_body.h): the workspace, its generation words
 // and the error word are shared with the per-query-head kernels, so launches of both kinds may alternate on one workspace.
+//
+// HL (head pruning, opt-in: SPATTEN_DECODE_GROUPED_HEADS): the step carries the device list of kept heads and / or the head
+// importance accumulator.  The grid stays (S, Hkv, B) — the host cannot read the list.  Every wave derives the LIVE MASK of its group
+// from the ascending list (bit g: head hkv G + g is listed) with loads issued next to the query rows.  A group without a live head
+// drains its requests and returns: no append, no stash, no partial, no ticket, no generation word — as in the per-query-head
+// form, where only launched heads append.  Otherwise the stream runs as always and the mask stands wherever `col < G` let a
+// head's results leave the workgroup: pruned heads' rows of out / stash / lse / importance_acc / head_abs_acc and of the workspace
+// are left untouched, and what their (possibly non-finite) query and previous stash rows hold reaches nothing: the query columns are
+// zeroed by a select; the first two tiles' previous-row requests go out BEFORE the mask is known, so pruned heads' previous rows of
+// those tiles still land in LDS (later tiles do not request them) — no lane reads them, the read is gated by the mask.  A live head's bits are
+// the plain grouped step's.  head_abs_acc[b H + h] += sum_e |out[b, h d + e]| over the rounded values the launch leaves in `out`, added
+// by the head's merger in a fixed order (two wave sums, then their sum): run-to-run identical, but NOT the per-query-head kernel's
+// order (decode_body.h add_head_abs sums its waves differently) — the two forms agree to fp32 rounding, not bit for bit.
 #include <stdlib.h>
 
 #include "common.h"
@@ -58,6 +71,8 @@ struct GqaParams {
   // CASC (cascade importance, deferred by one step: decode_body.h): the previous step's stash + (max, sum) folded into acc [H, >= N]
   // (behind the plain step's arguments: their offsets are those of the instantiations without the fold)
   const T* prev_scores; int64_t pv_sb, pv_sh; float* prev_lse; float* acc; int64_t acc_sh; int prev_len;
+  // HL (head pruning): the ascending device list of kept heads (nullptr: all), its length, the head importance accumulator [B * H]
+  const int32_t* head_ids; int n_active; float* head_abs;
 };
 
 // s_waitcnt vmcnt(n) only (gfx9 encoding: vmcnt in bits 3:0 and 15:14; expcnt / lgkmcnt left at "no wait")
@@ -74,7 +89,7 @@ template <int N> __device__ inline void wait_vm() {
 // with key < prev_len — the per-query-head kernel's expression, term for term.  The vmcnt waits below grow by exactly the added
 // requests.  The (max, sum) rows and the keys of the 16-byte piece that the previous rows' bound cuts (LDS-DMA moves whole pieces;
 // nothing is read past the bound) are ordinary loads issued in front of the first tile.
-template <typename T, bool DYN, bool CASC = false>
+template <typename T, bool DYN, bool CASC = false, bool HL = false>
 __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p) {
   constexpr int D = 128, KK = D / 16, DB = D / 32, KT = 32, NW = 4;
   constexpr int KBYTES = KT * D * 2;                  // a tile's key rows (8 KiB); as many value rows
@@ -197,6 +212,14 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
       for (int e = 0; e < 4; ++e) tail_b[e] = pr2[max(min(p_c8 + 4 * hi + e, p_clamp - 1), 0)];
     }
   }
+  // HL: the lane's entries of the head list (one per 64; the first two go out here, in front of the tile requests — lists beyond
+  // 128 heads finish where the mask is resolved).  -1: no entry.
+  int hl_id[2] = {-1, -1};
+  if (HL && p.head_ids != nullptr) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (lane + 64 * j < p.n_active) hl_id[j] = p.head_ids[lane + 64 * j];
+  }
   raw_t q_raw[KK / 2][4];
   {
     const int gq = min(col, G - 1);
@@ -235,6 +258,34 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   if (wave + NW < nt_bound) dma_tile(wave + NW, 1);
   SPATTEN_GSTAMP(1);          // two tiles requested
   __builtin_amdgcn_sched_barrier(0);
+  // HL: the group's live mask, resolved where the query rows are waited for.  A listed head h belongs to this group iff
+  // h / G == hkv (unsigned: an entry that is no head id matches no group); every wave ORs its lanes' bits for itself.
+  unsigned live_mask = G >= 32 ? 0xFFFFFFFFu : (1u << G) - 1u;
+  if (HL && p.head_ids != nullptr) {
+    unsigned m = 0u;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if ((unsigned)hl_id[j] / (unsigned)G == (unsigned)hkv) m |= 1u << ((unsigned)hl_id[j] % (unsigned)G);
+    for (int i = lane + 128; i < p.n_active; i += 64) {
+      const unsigned id = (unsigned)p.head_ids[i];
+      if (id / (unsigned)G == (unsigned)hkv) m |= 1u << (id % (unsigned)G);
+    }
+#pragma unroll
+    for (int x = 1; x < 64; x <<= 1) m |= (unsigned)__shfl_xor((int)m, x);
+    live_mask = __builtin_amdgcn_readfirstlane(m);
+    if (live_mask == 0u) {     // nobody of the group survives: what was requested lands in this workgroup's LDS, nothing else happens
+      wait_vm<0>();
+      return;
+    }
+    if (CASC) {                // later tiles request no previous rows of pruned heads
+#pragma unroll
+      for (int r = 0; r < NP; ++r)
+        if (!((live_mask >> ((16 * r + (lane >> 2)) & 31)) & 1u)) p_voff[r] = -1;
+    }
+  }
+  // does this lane's column hold a head whose results leave the workgroup?  (HL: bits >= G of the mask are never set; evaluated at
+  // every use, so the instantiations without HL keep the `col < G` they always had — and their instruction streams)
+  auto col_live = [&]() { return HL ? ((live_mask >> col) & 1u) != 0u : col < G; };
   frag qf[KK];                                        // rotated (modify_llama.py:92: three rounded ops)
   {
     const float live = col < G ? 1.f : 0.f;
@@ -247,7 +298,13 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
       V8::unpack(q_raw[kk][3], ss);
       rope_pair<T>(xlo, xhi, cc, ss, ylo, yhi);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { qf[kk][e] = DT<T>::from_f32(ylo[e] * live); qf[kk + KK / 2][e] = DT<T>::from_f32(yhi[e] * live); }
+      for (int e = 0; e < 8; ++e) {
+        if (HL) {   // a select: a pruned head's row may hold anything (0 x NaN is NaN)
+          qf[kk][e] = DT<T>::from_f32(col_live() ? ylo[e] : 0.f); qf[kk + KK / 2][e] = DT<T>::from_f32(col_live() ? yhi[e] : 0.f);
+        } else {
+          qf[kk][e] = DT<T>::from_f32(ylo[e] * live); qf[kk + KK / 2][e] = DT<T>::from_f32(yhi[e] * live);
+        }
+      }
     }
   }
 
@@ -272,7 +329,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   }
 
   const float rsqrt_d = 1.0f / p.sqrt_d;
-  T* stashp = (p.scores != nullptr && col < G) ? p.scores + b * p.sc_sb + (int64_t)(hkv * G + col) * p.sc_sh : nullptr;
+  T* stashp = (p.scores != nullptr && col_live()) ? p.scores + b * p.sc_sb + (int64_t)(hkv * G + col) * p.sc_sh : nullptr;
   float* lse_cur = p.lse;
   const int prev_len = !CASC ? 0 : DYN ? __builtin_amdgcn_readfirstlane(pl_dyn) : p.prev_len;
   float casc_m = 0.f, casc_rl = 0.f;
@@ -280,7 +337,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   float* accp = nullptr;
   if (CASC) {
     if (DYN && odd) {                                 // the writing side follows the parity too
-      if (col < G) stashp = const_cast<T*>(p.prev_scores) + b * p.pv_sb + (int64_t)(hkv * G + col) * p.pv_sh;
+      if (col_live()) stashp = const_cast<T*>(p.prev_scores) + b * p.pv_sb + (int64_t)(hkv * G + col) * p.pv_sh;
       lse_cur = p.prev_lse;
     }
     const float pm = odd ? ml_b[0] : ml_a[0], pl = odd ? ml_b[1] : ml_a[1];
@@ -469,7 +526,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
       // the previous step's probability of the lane's 16 keys (their rows came in front of the values: landed): register group q4
       // = keys row0 + 8 q4 + 4 hi + 0..3 = half `hi` of logical piece q4 of the head's 64 bytes.  (The atomics are requests of the
       // wave like the stash stores: they may only make a later wait longer.)
-      if (col < G && row0 < prev_len) {
+      if (col_live() && row0 < prev_len) {
         const char* pa = wbuf + stage * STAGE + 2 * KBYTES + col * 64 + hi * 8;
         const int sw = (col >> 2) & 3;
 #pragma unroll
@@ -518,7 +575,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     SPATTEN_GSTAMP(7);        // stream done
     const float l_col = xor32_sum(l_run);
     float* part = reinterpret_cast<float*>(wbuf);
-    if (col < G) {
+    if (col_live()) {
 #pragma unroll
       for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -532,9 +589,16 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   SPATTEN_GSTAMP(8);          // all waves' partials in LDS
 
   // ---- fold the waves, publish the split's partial per head ---------------------------------------------------------------------------
+  // HL: a head's importance term, one partial sum per wave of the 128 threads that hold its output row, parked in LDS behind
+  // the largest set of wave partials (32 columns x PITCH floats of wave 0's ring; the ring is 32 KiB) until the adds below
+  // (the merge's `fold`, [D][3] floats at the start of the same ring, ends below it too)
+  float* const habs = reinterpret_cast<float*>(lds) + 32 * PITCH;      // [G][2]
+  static_assert(!HL || (32 * PITCH + 64) * 4 <= WBUF, "head importance partials");
+  static_assert(3 * D <= 32 * PITCH, "the merge's fold buffer must end below the head importance partials");
   const int items = G * D;                            // (head of the group, output element)
   for (int idx = tid; idx < items; idx += 256) {
     const int g = idx >> 7, e = idx & (D - 1);
+    if (HL && !((live_mask >> g) & 1u)) continue;     // (uniform over the two waves of a head)
     float mw[NW], mwg = -INFINITY;
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
@@ -554,12 +618,20 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     if (p.S == 1) {
       p.out[b * p.out_sb + (int64_t)(hkv * G + g) * D + e] = DT<T>::from_f32(o_tot / l_tot);
       if (lse_cur != nullptr && e == 0) { lse_cur[2 * unit] = mwg; lse_cur[2 * unit + 1] = l_tot; }
+      if (HL && p.head_abs != nullptr) {
+        const float v = wave_sum(fabsf(DT<T>::round(o_tot / l_tot)));
+        if (lane == 0) habs[2 * g + (wave & 1)] = v;
+      }
       continue;
     }
     unsigned long long* part = p.ws_part + (int64_t)unit * p.ws_unit + (int64_t)split * (D + 2);
     const unsigned tag = (s_gen[g] & 0x7FFFFFFFu) + 1u;
     store_granule(part + e, o_tot, tag);
     if (e == 0) { store_granule(part + D, mwg, tag); store_granule(part + D + 1, l_tot, tag); }
+  }
+  if (HL && p.S == 1 && p.head_abs != nullptr) {
+    __syncthreads();
+    if (tid < G && ((live_mask >> tid) & 1u)) p.head_abs[unit0 + tid] += habs[2 * tid] + habs[2 * tid + 1];
   }
   if (p.S == 1) return;
   SPATTEN_GSTAMP(9);          // partial published (issued)
@@ -578,6 +650,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   float* const fold = reinterpret_cast<float*>(lds);  // [D][3] of the upper half (the wave partials are dead behind the barrier below)
   constexpr int KB = 16;
   for (int g = 0; g < G; ++g) {
+    if (HL && !((live_mask >> g) & 1u)) continue;                        // a pruned head: nobody polls for it, nothing of it moves
     if (p.poll_merge && split != p.S - 1 - (g % p.S)) continue;          // (workgroup-uniform)
     const int e = tid & (D - 1), half = tid >> 7;
     const int unit = unit0 + g;
@@ -648,7 +721,16 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
         p.ws_cnt[2 * unit + 1] = gen + 1u;            // next launch: new tag
       }
     }
+    if (HL && p.head_abs != nullptr) {                // (waves 0 and 1 are `half == 0`: the row this launch leaves in `out`)
+      const float v = wave_sum(half == 0 ? fabsf(DT<T>::round(og / lg)) : 0.f);
+      if (half == 0 && lane == 0) habs[2 * g + wave] = v;
+    }
     SPATTEN_GSTAMP(11);       // merged head stored
+  }
+  if (HL && p.head_abs != nullptr) {
+    __syncthreads();
+    if (tid < G && ((live_mask >> tid) & 1u) && (!p.poll_merge || split == p.S - 1 - (tid % p.S)))
+      p.head_abs[unit0 + tid] += habs[2 * tid] + habs[2 * tid + 1];
   }
   if (!p.poll_merge && tid == 0) __hip_atomic_store(p.ws_cnt + 2 * unit0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm
 }
@@ -692,14 +774,20 @@ static inline void gqa_layout(int cols, int lay, int n_splits, int ws_splits, in
 // Is this (validated: decode_rows) launch one the matrix-core form serves under the current mode, and with which split layout?  The ONE
 // eligibility routine: decode_gqa_rows launches by it and spatten_decode_gqa_form answers by it.  Host arithmetic only.
 // Served: the single-row step of a grouped-query model (16-bit, d = 128, G <= 32), with or without append, stash, (max, sum),
-// device-length state and the fused cascade accumulation (importance_acc + prev_*).  Not served: mask, head list, head
-// importance, quantised keys, fused projections, flags.
+// device-length state and the fused cascade accumulation (importance_acc + prev_*); with SPATTEN_DECODE_GROUPED_HEADS in the flags
+// also the head list and the head importance (the HL instantiations).  Not served: mask, quantised keys, fused projections, any
+// other flag — and a head list / head importance without that flag.
 bool decode_gqa_plan(const DecodeCall& c, int& S, int& chunk32) {
   const int mode = gqa_mode();
   if (mode == 0 || c.heads == c.kv_heads || c.head_dim != 128 || (c.dtype != SPATTEN_BF16 && c.dtype != SPATTEN_F16)) return false;
-  if (c.n_q != 1 || c.mask || c.pq || c.qkv_x || c.head_ids || c.head_abs || c.flags != 0 || c.causal ||
+  if (c.n_q != 1 || c.mask || c.pq || c.qkv_x || (c.flags & ~SPATTEN_DECODE_GROUPED_HEADS) != 0 || c.causal ||
       !c.q || !c.kr_cache || !c.v_cache || !c.out)
     return false;
+  if (c.head_ids || c.head_abs) {
+    // opt-in, and mode 1 only: no head-list step has been timed in both forms (the rule the accumulation steps follow below)
+    if (!(c.flags & SPATTEN_DECODE_GROUPED_HEADS) || mode < 0) return false;
+    if (c.head_ids && (c.n_active <= 0 || c.n_active > c.heads)) return false;
+  }
   if (c.kv_heads <= 0 || c.heads % c.kv_heads != 0) return false;
   const int G = c.heads / c.kv_heads;
   if (G > 32 || c.lse_q > 1) return false;
@@ -739,6 +827,7 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   const int cols = c.batch * c.kv_heads;
   // (a static step with nothing to fold — prev_len = 0 — is the plain step: no previous row need exist)
   const bool casc = c.acc != nullptr && (c.step != nullptr || c.prev_len > 0);
+  const bool hl = c.head_ids != nullptr || c.head_abs != nullptr;      // (the plan admitted them: the flag is set)
   const int poll_merge = (S > 1 && (long long)S * cols <= coresident_workgroups()) ? 1 : 0;
   const size_t cnt_bytes = decode_cnt_bytes(c.ws_units);
 
@@ -763,6 +852,7 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   p.lse = c.lse;                                                                                                 \
   p.prev_scores = (const T*)c.prev_scores; p.pv_sb = c.pv_sb; p.pv_sh = c.pv_sh; p.prev_lse = (float*)c.prev_lse;  \
   p.acc = c.acc; p.acc_sh = c.acc_sh; p.prev_len = c.prev_len;                                                   \
+  p.head_ids = c.head_ids; p.n_active = c.head_ids ? c.n_active : 0; p.head_abs = c.head_abs;                    \
   p.ws_err = (unsigned*)c.workspace;                                                                             \
   p.ws_cnt = c.workspace ? (unsigned*)((char*)c.workspace + kDecodeWsHeader) : nullptr;                          \
   p.ws_part = c.workspace ? (unsigned long long*)((char*)c.workspace + kDecodeWsHeader + cnt_bytes) : nullptr;   \
@@ -770,7 +860,12 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   p.B = c.batch; p.H = c.heads; p.Hkv = c.kv_heads; p.G = G; p.N = c.kv_len; p.S = S; p.chunk = chunk32;         \
   p.poll_merge = poll_merge; p.sqrt_d = sqrtf((float)c.head_dim);                                                \
   const dim3 grid(S, c.kv_heads, c.batch);                                                                       \
-  if (casc) {                                                                                                    \
+  if (hl) {                                                                                                      \
+    if (casc && c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true, true, true>), grid, dim3(256), 0, stream, p);        \
+    else if (casc) hipLaunchKernelGGL((decode_gqa_kernel<T, false, true, true>), grid, dim3(256), 0, stream, p);            \
+    else if (c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true, false, true>), grid, dim3(256), 0, stream, p);          \
+    else hipLaunchKernelGGL((decode_gqa_kernel<T, false, false, true>), grid, dim3(256), 0, stream, p);                     \
+  } else if (casc) {                                                                                                    \
     if (c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true, true>), grid, dim3(256), 0, stream, p);           \
     else hipLaunchKernelGGL((decode_gqa_kernel<T, false, true>), grid, dim3(256), 0, stream, p);                 \
   } else if (c.step) hipLaunchKernelGGL((decode_gqa_kernel<T, true>), grid, dim3(256), 0, stream, p);            \

@@ -27,7 +27,7 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
                        prefill_stash=True, assume_causal=False, head_keep=None, pq_threshold=None, local_v_keep=None,
                        layer_keep=None, fuse_qkv=False, native_gemv=False, head_parallel=None, numerics="auto",
                        auto_graph=False, pq_profile=None, fused_step=False, token_scope="head", pq_query_bits=None, pq_grouped=False,
-                       pq_cascade=False):
+                       pq_cascade=False, grouped_head_pruning=False):
     """The reference's four positional arguments (enable_spatten_llm.py:5) plus opt-in extensions:
 
     ``prefill_stash=False``: forwards with ``q_len > 1`` do not materialise ``self.attn_scores`` ([B,H,q,N]: 4 GiB per
@@ -91,7 +91,11 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
     into its two launches — spatten_attn_decode_pq_cascade; every V row is read and there is no select / gather launch; carries
     ``head_keep`` and is captured by ``auto_graph``.  Measured 29.4 us per layer-step against 74.9 for
     ``local_v_keep=1.0`` and 26.1 for the profiled step without importance, 40 heads x 8192 rows, DESIGN 3.7: the route to prefer when
-    every V row is kept), ``layer_keep`` (layer-to-layer cascade token
+    every V row is kept), ``grouped_head_pruning`` (with ``head_keep`` on a grouped-query model: the plain decode step hands its
+    head list and head importance to the matrix-core grouped form — ``ops.attn_decode(grouped_heads=True)`` — where a pruned head
+    costs nothing and a KV head without a surviving query head streams nothing; the form is taken under
+    ``ops.set_decode_gqa(1)`` only, which the caller sets: the option leaves the process-wide mode alone.  The PQ, local-V and
+    chained routes stay on their kernels; no effect on an MHA model.  Correct, opt-in, speed not measured), ``layer_keep`` (layer-to-layer cascade token
     pruning: one important-token count per layer, non-increasing — the surviving set shrinks through the layers),
     ``token_scope="global"`` (ONE kept token set per layer shared by all heads, ranked by the importance summed over the
     heads — README.md:21, workloads/small.csv:1; head-parallel ranks all-reduce the [layers, L] sums once per prune event;
@@ -163,7 +167,7 @@ def enable_spatten_llm(model, start_size, important_size, recent_size, importanc
         cache.ext = SpattenExtensions(cache, len(mods), cascade=importance_mode == "cascade", head_keep=head_keep,
                                       pq_threshold=pq_threshold, local_v_keep=local_v_keep, layer_keep=layer_keep,
                                       head_parallel=head_parallel, pq_profile=pq_profile, pq_query_bits=pq_query_bits,
-                                      pq_grouped=pq_grouped, pq_cascade=pq_cascade)
+                                      pq_grouped=pq_grouped, pq_cascade=pq_cascade, grouped_head_pruning=grouped_head_pruning)
         for layer, m in enumerate(mods):
             m._spatten_ext = (cache.ext, layer)
     if auto_graph:

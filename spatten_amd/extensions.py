@@ -38,6 +38,11 @@ against those restatements.
     pq_profile + pq_cascade     the profiled step with the cumulative importance folded into its two launches
                                 (spatten_attn_decode_pq_cascade): importance_mode="cascade" on the profiled planes with every V row
                                 read and no select / gather launches; with or without head_keep
+    grouped_head_pruning=True   with head_keep on a grouped-query model: the plain decode step passes its head list / head
+                                importance to the matrix-core grouped form (ops.attn_decode(grouped_heads=True)), which takes
+                                it under ops.set_decode_gqa(1) only — the option does not touch that process-wide mode.  The
+                                PQ, local-V and chained routes stay on their kernels; no effect on an MHA model.  Correct;
+                                speed not measured.
     layer_keep=[k_0..k_L-1]     layer-to-layer cascade token pruning (README.md:11; the traces' key_fetch_num shrinks layer
                                 by layer): at a prune event layer l keeps k_l tokens of its window, chosen among the
                                 tokens layer l-1 just kept — the surviving set shrinks through the layers.  Caches of
@@ -122,7 +127,8 @@ class SpattenExtensions:
                  head_keep: Union[None, int, Sequence[int]] = None, pq_threshold: Optional[float] = None,
                  local_v_keep: Optional[float] = None, layer_keep: Optional[Sequence[int]] = None, head_parallel=None,
                  pq_profile: Optional[Sequence[int]] = None, pq_query_bits: Optional[int] = None, pq_grouped: bool = False,
-                 pq_cascade: bool = False):
+                 pq_cascade: bool = False, grouped_head_pruning: bool = False):
+        self.grouped_head_pruning = bool(grouped_head_pruning)
         if pq_cascade:
             if pq_profile is None or not cascade:
                 raise ValueError("pq_cascade needs pq_profile and importance_mode='cascade' (it is the profiled decode step with "
@@ -313,7 +319,8 @@ class SpattenExtensions:
             return st.out, st.stash[cur][:, :, None, :kv_len]
         ops.attn_decode(q, slab.k, slab.kr, slab.v, cap, cos, sin, 0, k_new=k_new, v_new=v_new, out=st.out,
                         scores=st.stash[0], lse=st.lse[0], head_ids=st.head_ids, cascade=casc,
-                        head_abs=st.head_abs if self.head_keep is not None else None, step=step)
+                        head_abs=st.head_abs if self.head_keep is not None else None, step=step,
+                        grouped_heads=self.grouped_head_pruning)
         cur = (gctx.steps_traced & 1) if self.cascade else 0
         return st.out, st.stash[cur][:, :, None, :kv_len]
 
@@ -386,7 +393,7 @@ class SpattenExtensions:
             # bit for bit — kv_slab.KVSlab.decode_step)
             ops.attn_decode(q, slab.k, slab.kr, slab.v, kv_len, cos, sin, past_len, k_new=k_new, v_new=v_new,
                             out=st.out, scores=stash, lse=lse, head_ids=st.head_ids, cascade=casc, head_abs=head_abs,
-                            layout=slab.capacity)
+                            layout=slab.capacity, grouped_heads=self.grouped_head_pruning)
         if self.cascade:
             st.pending_len = kv_len
         return st.out, stash[:, :, None, :kv_len]

@@ -164,7 +164,8 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
                 head_ids: Optional[torch.Tensor] = None, scores_only: bool = False,
                 cascade: Optional[tuple] = None, pq: Optional[tuple] = None,
                 head_abs: Optional[torch.Tensor] = None, step: Optional["StepState"] = None,
-                layout: int = 0, proj: Optional[tuple] = None, gqa_form: bool = False) -> torch.Tensor:
+                layout: int = 0, proj: Optional[tuple] = None, gqa_form: bool = False,
+                grouped_heads: bool = False) -> torch.Tensor:
     """Fused decode attention (modify_llama.py:86-147 at q_len=1).
 
     q [B,H,d]; k_cache (un-rotated, only appended to) / kr_cache (rotated shadow, see build_shadow) /
@@ -187,6 +188,9 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     the same C call (a second launch of spatten_gemv's kernel: one host call per layer-step); ``proj_out`` is filled.
     gqa_form: build the argument block, launch NOTHING and return whether the call would run in the matrix-core grouped-query
     form under the current mode (spatten_decode_gqa_form; see decode_gqa_form).
+    grouped_heads: opt-in (SPATTEN_DECODE_GROUPED_HEADS) — a step that carries ``head_ids`` / ``head_abs`` may take the matrix-core
+    grouped-query form, under ``set_decode_gqa(1)`` only: a pruned head costs nothing, a group without a survivor streams and
+    appends nothing.  Without a head list and ``head_abs`` it changes nothing.  Correct; speed not measured.
     Returns out [B, H*d]."""
     _dev(q, k_cache, kr_cache, v_cache, cos, sin, k_new, v_new, mask, out, scores, lse, position_ids, head_abs)
     if position_ids is not None and position_ids.dtype != torch.int64:
@@ -239,7 +243,7 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     a.batch, a.heads, a.kv_heads, a.head_dim, a.kv_len, a.pos_q, a.n_splits = B, H, Hkv, d, kv_len, pos_q, n_splits
     if head_ids is not None:
         a.head_ids, a.n_active_heads = head_ids.data_ptr(), head_ids.numel()
-    a.flags = 1 if scores_only else 0
+    a.flags = (1 if scores_only else 0) | (2 if grouped_heads else 0)
     if proj is not None:
         _fill_proj(a, proj, q, B, H * d)
     a.kv_len_layout = int(layout)
