@@ -139,7 +139,9 @@ int spatten_attn_decode(int dtype,
  *                              head; pass 2 = flagged heads refetch the LSB plane and are recomputed once, confident heads
  *                              return at once).  pq_need_lsb: int32 [B*H] scratch / output (required).  k_new and flags
  *                              must be NULL / 0 in this mode (append with spatten_kv_append + spatten_pq_pack first);
- *                              `scores` then holds the logits of the quantised keys that the output was computed from. */
+ *                              `scores` then holds the logits of the quantised keys that the output was computed from.
+ *   step_state / step_state_sb device-resident cache length ("Device-resident step state" below); with a non-zero stride one
+ *                              state PER SEQUENCE: a ragged batch on the fast kernels, without a mask tensor. */
 #define SPATTEN_DECODE_SCORES_ONLY 1
 #define SPATTEN_DECODE_GROUPED_HEADS 2
 typedef struct spatten_decode_args {
@@ -169,7 +171,10 @@ typedef struct spatten_decode_args {
                                       split) is laid out for THIS length, so steps at different lengths share it — a static
                                       launch and a step_state launch whose bound (its kv_len) is this value add their
                                       partials in the same order: bit-identical outputs.  Later splits may then be empty. */
-  int32_t pad3_;
+  int32_t step_state_sb;           /* with step_state: BYTES between the states of consecutive sequences of the batch — sequence b
+                                      reads its length, query position and append slot from step_state + b * step_state_sb (a
+                                      ragged batch; see "One state per sequence" below).  0 = one state for the whole batch.
+                                      (The block's former pad word: callers zero-fill the block, its size and offsets stand.) */
   /* ABI 3: the output projection of the step (modify_llama.py:163) in the same CALL: proj_out[b, n] = sum_k out[b, k] *
      proj_weight[n, k] (+ proj_bias[n]); weight [proj_n, heads*head_dim] row stride proj_w_sn (elements), output row stride
      proj_out_sb.  `out` is still written; the projection is a second launch (spatten_gemv's kernel: bit-identical with
@@ -306,6 +311,21 @@ int spatten_attn_decode_chain(const spatten_chain_args_t* args, void* stream);
  * A token of a captured graph = spatten_step_advance(state, ..., 1) followed by the layers' spatten_attn_decode_args
  * launches sharing the state; before the first replay of a turn: spatten_step_set(state, ..., cache_len, cache_len - 1).
  * The state is spatten_step_state_bytes(dtype, head_dim) bytes of device memory owned by the caller.
+ *
+ * One state per sequence (spatten_decode_args_t::step_state_sb != 0) — a RAGGED batch: prompts differ in length, and a pruned
+ * sequence has another length and position than one that was not pruned.  `step_state` is then an array of `batch` states,
+ * step_state_sb bytes apart (a multiple of 256, >= spatten_step_state_bytes(); else SPATTEN_ERR_INVALID, as is a stride without
+ * step_state), and sequence b of the launch reads ITS state: its length (1 <= length_b <= kv_len, the common bound), its query's
+ * rotary row and its append slot — k_new / v_new of sequence b go to row length_b - 1 of sequence b's planes.  Everything above
+ * holds per sequence: rows [length_b, bound) of sequence b's kr_cache / v_cache must be finite, its stash entries
+ * [length_b, bound) are left untouched.  The launch is laid out for the bound and STREAMS THE BOUND for every sequence: a ragged
+ * batch saves no bytes against a padded one — what it buys is the kernels a mask shuts the step out of (the lean step, the
+ * matrix-core grouped-query form), the captured graph, the per-sequence append slot and position, and no mask tensor.
+ * Served by every route of the plain step (per-query-head and grouped-query kernels, all dtypes and head dims); head_ids,
+ * head_abs_acc, SPATTEN_DECODE_GROUPED_HEADS, scores, lse, k_new / v_new and proj_* are admitted as with one state; mask,
+ * position_ids and SCORES_ONLY stay refused.  SPATTEN_ERR_UNSUPPORTED with importance_acc (the accumulator [H, L] has no batch
+ * axis: fold a sequence's stash and lse with spatten_importance_accumulate on a slice), pq_* and qkv_*.  The chained launch, the
+ * profiled-plane / local-V entry points and spatten_kv_append_step keep the one shared state.
  * ---------------------------------------------------------------------------------------------- */
 size_t spatten_step_state_bytes(int dtype, int head_dim);
 /* state := (kv_len, pos_q) from HOST values + the rotary rows of positions pos_q and kv_len - 1 (cos / sin: the half tables
@@ -316,6 +336,18 @@ int spatten_step_set(void* state, int dtype, int head_dim, const void* cos, cons
  * values of the length, hence capturable. */
 int spatten_step_advance(void* state, int dtype, int head_dim, const void* cos, const void* sin, int table_rows,
                          int delta, void* stream);
+/* The same for `batch` states state_stride BYTES apart (one per sequence, see above; batch > 1: a multiple of 256 and >=
+ * spatten_step_state_bytes()), ONE launch each, one workgroup per sequence.  The values are DEVICE int32 [batch]: state b :=
+ * (kv_lens[b], pos_q[b]) (negative values are stored as 0), resp. state b += deltas[b] (deltas NULL: `delta` for every sequence; a
+ * sequence with delta 0 keeps its length and position — but a decode launch still runs it and writes its k_new / v_new to row
+ * length - 1 again: hand it the rows of its last step once more, or accept the overwrite; its word 2 still counts the step).  Pure stream operations without host values of the lengths — both are
+ * capturable, the set included.  Words 2 / 3 of each state behave as in the scalar calls; with batch == 1 they leave the state
+ * bytes spatten_step_set / _advance leave for the same values; state_stride is then neither used nor checked (spatten_attn_decode_args
+ * checks a non-zero step_state_sb for every batch size: pass a valid stride, or 0, with one sequence). */
+int spatten_step_set_batch(void* states, int64_t state_stride, int batch, int dtype, int head_dim, const void* cos, const void* sin,
+                           int table_rows, const int32_t* kv_lens, const int32_t* pos_q, void* stream);
+int spatten_step_advance_batch(void* states, int64_t state_stride, int batch, int dtype, int head_dim, const void* cos, const void* sin,
+                               int table_rows, int delta, const int32_t* deltas, void* stream);
 
 /* The append of ONE decode step in device-length form, for the modes whose attention launch appends nothing (pq_*):
  * row (state word 0) - 1 of k_cache (optional) / v_cache <- k_new / v_new [B,Hkv,d] (strides new_sb, new_sh), of kr_cache

@@ -38,7 +38,7 @@ class DecodeArgs(ctypes.Structure):
         ("pq_pl_sb", c_int64), ("pq_pl_sh", c_int64), ("pq_sc_sb", c_int64), ("pq_sc_sh", c_int64),
         ("pq_threshold", c_float), ("pad2_", c_int32),
         ("pq_need_lsb", c_void_p),
-        ("step_state", c_void_p), ("kv_len_layout", c_int32), ("pad3_", c_int32),
+        ("step_state", c_void_p), ("kv_len_layout", c_int32), ("step_state_sb", c_int32),
         ("proj_weight", c_void_p), ("proj_w_sn", c_int64), ("proj_bias", c_void_p), ("proj_out", c_void_p),
         ("proj_out_sb", c_int64), ("proj_n", c_int32), ("pad4_", c_int32),
         ("qkv_x", c_void_p), ("qkv_weight", c_void_p), ("qkv_w_sn", c_int64), ("qkv_bias", c_void_p),
@@ -185,6 +185,10 @@ def _declare(lib):
     lib.spatten_step_set.argtypes = [p, i, i, p, p, i, i, i, p]
     lib.spatten_step_advance.restype = c_int
     lib.spatten_step_advance.argtypes = [p, i, i, p, p, i, i, p]
+    lib.spatten_step_set_batch.restype = c_int
+    lib.spatten_step_set_batch.argtypes = [p, i64, i, i, i, p, p, i, p, p, p]
+    lib.spatten_step_advance_batch.restype = c_int
+    lib.spatten_step_advance_batch.argtypes = [p, i64, i, i, i, p, p, i, i, p, p]
     lib.spatten_gemv.restype = c_int
     lib.spatten_gemv.argtypes = [i, p, i64, p, i64, p, p, i64, i, i, i, p]
     lib.spatten_kv_append.restype = c_int

@@ -457,6 +457,7 @@ struct DecodeCall {
   float* acc = nullptr; int64_t acc_sh = 0; int prev_len = 0;
   float* head_abs = nullptr;   // [B*H] head importance accumulators (n_q == 1 only)
   const void* step = nullptr;  // device-resident step state (step.hip): kv_len above is then a bound
+  int step_sb = 0;             // bytes between the states of consecutive sequences (spatten_decode_args_t::step_state_sb; 0: one state)
   int layout_len = 0;          // > kv_len: lay the splits out for this length (spatten_decode_args_t::kv_len_layout)
   // fused / trailing output projection (spatten_decode_args_t::proj_*)
   const void* proj_w = nullptr; int64_t proj_w_sn = 0; const void* proj_bias = nullptr; void* proj_out = nullptr;

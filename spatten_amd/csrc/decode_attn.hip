@@ -515,6 +515,13 @@ static int decode_rows_check(const DecodeCall& c, int& n_active, int& S, int& ch
   // roles every step (same strides, rows up to the bound)
   if (c.step && c.acc && (!c.scores || !c.lse || !c.prev_scores || !c.prev_lse || c.pv_sb != c.sc_sb || c.pv_sh != c.sc_sh))
     return SPATTEN_ERR_INVALID;
+  // one state per sequence (a ragged batch): whole 256-byte lines apart, no two states overlapping.  The accumulator [H, L] has no
+  // batch axis, the quantised-key passes and the fused projections keep the shared state.
+  if (c.step_sb != 0) {
+    if (!c.step || c.step_sb % 256 != 0 || c.step_sb < 0 || (size_t)c.step_sb < spatten_step_state_bytes(c.dtype, c.head_dim))
+      return SPATTEN_ERR_INVALID;
+    if (c.acc || pq || c.qkv_x) return SPATTEN_ERR_UNSUPPORTED;
+  }
   if (c.head_dim != 64 && c.head_dim != 128 && c.head_dim != 256) return SPATTEN_ERR_UNSUPPORTED;
   if (c.dtype != SPATTEN_F32 && c.dtype != SPATTEN_F16 && c.dtype != SPATTEN_BF16) return SPATTEN_ERR_INVALID;
   const int units = c.batch * c.heads * c.n_q;          // workspace is indexed by the FULL head id
@@ -590,7 +597,8 @@ int decode_rows(const DecodeCall& c, hipStream_t stream) {
   p.k_new = (const T*)(c.k_new ? c.k_new : (c.q ? c.q : c.cos)); p.v_new = (const T*)(c.k_new ? c.v_new : (c.q ? c.q : c.cos)); \
   p.new_sb = c.k_new ? c.new_sb : c.q_sb; p.new_sh = c.k_new ? c.new_sh : c.q_sh;                        \
   p.cos = (const T*)c.cos; p.sin = (const T*)c.sin; p.table_rows = c.table_rows;                         \
-  p.step = (const int32_t*)c.step; p.nr_row = (c.kv_len < c.table_rows ? c.kv_len : c.table_rows) - 1;   \
+  p.step = (const int32_t*)c.step; p.step_sb = c.step_sb;                                                \
+  p.nr_row = (c.kv_len < c.table_rows ? c.kv_len : c.table_rows) - 1;                                    \
   if (c.step) {   /* the state's staged rotary rows stand in for the table: row 0 = query, row 1 = appended key */ \
     p.cos = (const T*)((const char*)c.step + kStepHeader);                                               \
     p.sin = p.cos + 2 * (c.head_dim / 2); p.table_rows = 2; p.nr_row = 1;                                \
@@ -695,7 +703,7 @@ static int decode_call_of(const spatten_decode_args_t* a, DecodeCall& c, PQKeys&
   c.prev_scores = a->prev_scores; c.pv_sb = a->prev_sb; c.pv_sh = a->prev_sh; c.prev_lse = a->prev_lse;
   c.acc = a->importance_acc; c.acc_sh = a->acc_sh; c.prev_len = a->prev_len;
   c.head_abs = a->head_abs_acc;
-  c.step = a->step_state; c.layout_len = a->kv_len_layout;
+  c.step = a->step_state; c.step_sb = a->step_state_sb; c.layout_len = a->kv_len_layout;
   c.proj_w = a->proj_weight; c.proj_w_sn = a->proj_w_sn; c.proj_bias = a->proj_bias; c.proj_out = a->proj_out;
   c.proj_out_sb = a->proj_out_sb; c.proj_n = a->proj_n;
   c.qkv_x = a->qkv_x; c.qkv_w = a->qkv_weight; c.qkv_w_sn = a->qkv_w_sn; c.qkv_bias = a->qkv_bias; c.qkv_xch = a->qkv_exchange;

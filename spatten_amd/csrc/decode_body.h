@@ -55,6 +55,7 @@ struct DecodeParams {
   T* kc; T* krc; T* vc; int64_t kv_sb, kv_sh;
   const T* k_new; const T* v_new; int64_t new_sb, new_sh;
   const T* cos; const T* sin; int table_rows;
+  int step_sb = 0;       // DYN: bytes between the step states of consecutive sequences (0: one state for the whole batch)
   const int64_t* pos_ids; int64_t pos_sb;
   const T* mask; int64_t mask_sb, mask_sq;
   T* out; int64_t out_sb, out_sq;
@@ -69,7 +70,8 @@ struct DecodeParams {
   float* head_abs;      // optional [B*H]: += sum_e |out[b, h, e]| (head importance, README.md:21), by the unit's last writer
   const int32_t* step;  // DYN: the device-resident step state (step.hip): word 0 = the cache length AFTER this step's append.
                         // N below is then only a BOUND (grid / chunk / load addresses come from it); cos / sin point at the
-                        // state's two staged rotary rows (row 0: the query's position, row 1: the appended key's slot)
+                        // state's two staged rotary rows (row 0: the query's position, row 1: the appended key's slot).
+                        // step_sb != 0: sequence b's state — its length and its rotary rows — lies b * step_sb bytes further on
   int nr_row;           // rotary-table row of the appended key's slot (N - 1; DYN: 1)
   unsigned long long* ws_part;   // [units][ws_unit] {value, tag} granules; split s of a unit at s * (D + 2)
   unsigned* ws_cnt;     // [units][2]: {arrival counter, launch generation}
@@ -205,9 +207,16 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
 
   // DYN: the length is requested FIRST (vector loads return in order: it is back before the query) and read after the
   // tile loads have been issued
+  // (a ragged batch: sequence b reads ITS state — length, query position's and append slot's rotary rows.  The static
+  //  instantiations keep p.cos / p.sin as they are; so do the fused-projection and the chained launch, which have one state)
+  constexpr bool RAGGED = DYN && !FUSED && !CHAIN;
+  const int64_t st_off = RAGGED ? (int64_t)b * p.step_sb : 0;
+  const int32_t* const stp = RAGGED ? reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p.step) + st_off) : p.step;
+  const T* const cosp = RAGGED ? reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.cos) + st_off) : p.cos;
+  const T* const sinp = RAGGED ? reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.sin) + st_off) : p.sin;
   int n_dyn = 0, cnt_dyn = 0, pl_dyn = 0;
-  if (DYN) n_dyn = p.step[opaque_lane(0)];
-  if (DYN && (CASC || KSRC == 2)) { cnt_dyn = p.step[2 + opaque_lane(0)]; pl_dyn = p.step[3 + opaque_lane(0)]; }
+  if (DYN) n_dyn = stp[opaque_lane(0)];
+  if (DYN && (CASC || KSRC == 2)) { cnt_dyn = stp[2 + opaque_lane(0)]; pl_dyn = stp[3 + opaque_lane(0)]; }
   // CASC: (max, sum) of the previous step's row, requested BEFORE the tile (r03: behind the tile these 8 bytes came back
   // after it — returns are in order — and the first accumulation waited for the whole stream); DYN: of both buffers
   float ml_a[2] = {0.f, 1.f}, ml_b[2] = {0.f, 1.f};
@@ -362,13 +371,13 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
       q_raw[0] = V8::ldg(qp + 8 * c);
       q_raw[1] = V8::ldg(qp + HALF + 8 * c);
     }
-    q_raw[2] = V8::ldg(p.cos + (int64_t)pq * HALF + 8 * c);
-    q_raw[3] = V8::ldg(p.sin + (int64_t)pq * HALF + 8 * c);
+    q_raw[2] = V8::ldg(cosp + (int64_t)pq * HALF + 8 * c);
+    q_raw[3] = V8::ldg(sinp + (int64_t)pq * HALF + 8 * c);
   }
   unsigned gen_f = 0, gen_y = 0;
   if (FUSED) {      // what does not depend on the projections goes out first; then B1: the projection waves are on their last pass
-    n_raw[0] = V8::ldg(p.cos + (int64_t)p.nr_row * HALF + 8 * c);
-    n_raw[1] = V8::ldg(p.sin + (int64_t)p.nr_row * HALF + 8 * c);
+    n_raw[0] = V8::ldg(cosp + (int64_t)p.nr_row * HALF + 8 * c);
+    n_raw[1] = V8::ldg(sinp + (int64_t)p.nr_row * HALF + 8 * c);
     gen_f = p.ws_cnt[(p.S > 1 ? 2 * unit + 1 : 0) + opaque_lane(0)];
     if (OPROJ) gen_y = p.ych_gen[opaque_lane(0)];
     // B1 — a bare s_barrier: __syncthreads() carries a fence, i.e. `s_waitcnt vmcnt(0)`, and the projection waves would
@@ -380,8 +389,8 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
     const T* kp = p.k_new + b * p.new_sb + hkv * p.new_sh;      // (always readable: see `append`)
     nk_raw[0] = V8::ldg(kp + 8 * c);
     nk_raw[1] = V8::ldg(kp + HALF + 8 * c);
-    n_raw[0] = V8::ldg(p.cos + (int64_t)p.nr_row * HALF + 8 * c);
-    n_raw[1] = V8::ldg(p.sin + (int64_t)p.nr_row * HALF + 8 * c);
+    n_raw[0] = V8::ldg(cosp + (int64_t)p.nr_row * HALF + 8 * c);
+    n_raw[1] = V8::ldg(sinp + (int64_t)p.nr_row * HALF + 8 * c);
   }
   if (!CHAIN) issue_values(tile_a, lo);
   if (!FUSED && !CHAIN) {

@@ -59,6 +59,7 @@ struct GqaParams {
   const T* q; int64_t q_sb, q_sh;
   T* kc; T* krc; T* vc; int64_t kv_sb, kv_sh;
   const T* k_new; const T* v_new; int64_t new_sb, new_sh; int append;
+  int step_sb = 0;                                          // DYN: bytes between the step states of consecutive sequences (0: one state)
   const T* cos; const T* sin; int table_rows, nr_row;      // rotary half tables [rows, D/2]; nr_row: the appended slot's row
   const int64_t* pos_ids; int64_t pos_sb; int pos_q;
   const int32_t* step;                                      // device-length form: word 0 = the live length (N is then the bound)
@@ -114,10 +115,16 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
   char* const wbuf = lds + wave * WBUF;
   SPATTEN_GSTAMP(0);
 
+  // DYN, a ragged batch (step_sb != 0): sequence b's own state — its length and its two staged rotary rows (b is uniform: the
+  // length stays a scalar load); the static instantiations keep p.cos / p.sin as they are
+  const int64_t st_off = DYN ? (int64_t)b * p.step_sb : 0;
+  const int32_t* const stp = DYN ? reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p.step) + st_off) : p.step;
+  const T* const cosp = DYN ? reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.cos) + st_off) : p.cos;
+  const T* const sinp = DYN ? reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.sin) + st_off) : p.sin;
   int n_live = p.N;
-  if (DYN) n_live = p.step[0];                        // (a scalar load: waited for behind the first tile's requests)
+  if (DYN) n_live = stp[0];                           // (a scalar load: waited for behind the first tile's requests)
   int cnt_dyn = 0, pl_dyn = 0;
-  if (CASC && DYN) { cnt_dyn = p.step[2]; pl_dyn = p.step[3]; }   // the state's step count (buffer parity) and previous length
+  if (CASC && DYN) { cnt_dyn = stp[2]; pl_dyn = stp[3]; }   // the state's step count (buffer parity) and previous length
 
   const T* krb = p.krc + b * p.kv_sb + hkv * p.kv_sh;
   const T* vb = p.vc + b * p.kv_sb + hkv * p.kv_sh;
@@ -226,8 +233,8 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     const T* qrow = p.q + b * p.q_sb + (int64_t)(hkv * G + gq) * p.q_sh;
     int ps = DYN ? 0 : (p.pos_ids ? (int)p.pos_ids[b * p.pos_sb] : p.pos_q);
     ps = min(max(ps, 0), p.table_rows - 1);
-    const T* cr = p.cos + (int64_t)ps * (D / 2);
-    const T* sr = p.sin + (int64_t)ps * (D / 2);
+    const T* cr = cosp + (int64_t)ps * (D / 2);
+    const T* sr = sinp + (int64_t)ps * (D / 2);
 #pragma unroll
     for (int kk = 0; kk < KK / 2; ++kk) {
       q_raw[kk][0] = V8::ldg(qrow + 16 * kk + 8 * hi);
@@ -323,8 +330,8 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     const int nr = DYN ? 1 : p.nr_row;
     nk_raw[0] = V8::ldg(kp + 8 * c8);
     nk_raw[1] = V8::ldg(kp + D / 2 + 8 * c8);
-    nk_raw[2] = V8::ldg(p.cos + (int64_t)nr * (D / 2) + 8 * c8);
-    nk_raw[3] = V8::ldg(p.sin + (int64_t)nr * (D / 2) + 8 * c8);
+    nk_raw[2] = V8::ldg(cosp + (int64_t)nr * (D / 2) + 8 * c8);
+    nk_raw[3] = V8::ldg(sinp + (int64_t)nr * (D / 2) + 8 * c8);
     nv_raw = V8::ldg(p.v_new + b * p.new_sb + hkv * p.new_sh + 8 * (lane & 15));
   }
 
@@ -839,7 +846,7 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   p.append = c.k_new != nullptr;                                                                                 \
   p.cos = (const T*)c.cos; p.sin = (const T*)c.sin; p.table_rows = c.table_rows;                                 \
   p.nr_row = (c.kv_len < c.table_rows ? c.kv_len : c.table_rows) - 1;                                            \
-  p.step = (const int32_t*)c.step;                                                                               \
+  p.step = (const int32_t*)c.step; p.step_sb = c.step_sb;                                                        \
   if (c.step) {   /* the state's staged rotary rows: row 0 = query, row 1 = appended key */                      \
     p.cos = (const T*)((const char*)c.step + kStepHeader);                                                       \
     p.sin = p.cos + 2 * (c.head_dim / 2); p.table_rows = 2; p.nr_row = 1;                                        \

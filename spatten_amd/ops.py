@@ -183,7 +183,8 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     head_abs fp32 [B*H]: += sum |out| per (b, h) (cumulative head importance for head pruning).
     layout: lay the split-N decomposition out for this length (>= kv_len) instead of kv_len.
     step (StepState): the device-resident length — ``kv_len`` is then the BOUND of the launch, ``pos_q`` is not read, rows
-    [length, bound) of kr_cache / v_cache must hold finite values.
+    [length, bound) of kr_cache / v_cache must hold finite values.  ``StepState(..., batch=B)``: a ragged batch — sequence b has
+    its own length, query position and append slot (the launch still streams the bound per sequence); not with cascade / pq.
     proj = (weight [N, H*d], bias [N] or None, proj_out [B, N]): the step's output projection (modify_llama.py:163) issued by
     the same C call (a second launch of spatten_gemv's kernel: one host call per layer-step); ``proj_out`` is filled.
     gqa_form: build the argument block, launch NOTHING and return whether the call would run in the matrix-core grouped-query
@@ -253,6 +254,10 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
         if scores is not None and scores.shape[2] < kv_len:
             raise ValueError("device-length step: the stash row must cover the bound")
         a.step_state = step.data_ptr()
+        if getattr(step, "batch", None) is not None:      # one state per sequence (ragged batch)
+            if step.batch != B:
+                raise ValueError(f"step state holds {step.batch} sequences, the launch has {B}")
+            a.step_state_sb = step.stride
     if cascade is not None:
         acc, prev_scores, prev_lse, prev_len = cascade
         _dev(acc, prev_scores, prev_lse)
@@ -482,9 +487,14 @@ class StepState:
     """Device-resident step state (include/spatten.h, ABI 3): the cache length after the next append, the query's rotary
     position and the rotary rows of both.  One per token stream (all layers of a model share it); ``advance`` is a stream
     operation without host values, so a token's launch sequence — advance, then every layer's decode launch with
-    ``step=state`` — is captured once into a HIP graph and replayed for each token."""
+    ``step=state`` — is captured once into a HIP graph and replayed for each token.
 
-    def __init__(self, cos: torch.Tensor, sin: torch.Tensor):
+    ``batch=B``: one state PER SEQUENCE of a ragged batch (``stride`` bytes apart; include/spatten.h, "one state per sequence"):
+    sequence b of a launch with ``step=state`` reads its own length, query position and append slot.  ``set`` / ``advance`` are
+    then one launch each over device values and ``read`` returns one tuple per sequence.  Capturable are ``advance(delta)`` and the
+    forms handed int32 DEVICE tensors; ints / host sequences are uploaded first (a pageable host-to-device copy: not inside a capture)."""
+
+    def __init__(self, cos: torch.Tensor, sin: torch.Tensor, batch: Optional[int] = None):
         _dev(cos, sin)
         self.lib = _lib.load()
         self.cos, self.sin = cos, sin                      # half tables [rows, d/2] in the model dtype (kept alive)
@@ -493,27 +503,72 @@ class StepState:
         nbytes = self.lib.spatten_step_state_bytes(self.dt, self.d)
         if nbytes == 0:
             raise ValueError("unsupported head_dim / dtype for a step state")
-        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=cos.device)
+        if batch is not None and int(batch) <= 0:
+            raise ValueError("StepState: batch must be positive")
+        self.batch = None if batch is None else int(batch)
+        self.stride = 0 if batch is None else int(nbytes)  # bytes between the states of consecutive sequences (0: one shared state)
+        self.buf = torch.zeros(nbytes * (self.batch or 1), dtype=torch.uint8, device=cos.device)
 
     def data_ptr(self) -> int:
         return self.buf.data_ptr()
 
-    def set(self, kv_len: int, pos_q: int):
-        """Host values -> state (not capturable: the values are launch arguments).  ``kv_len`` = the current cache length;
-        after the next ``advance()`` the state describes the step that appends row ``kv_len``."""
-        if max(kv_len, pos_q + 1) > self.cos.shape[0]:
-            raise ValueError("step state beyond the rotary table")
-        _lib.check(self.lib.spatten_step_set(self.buf.data_ptr(), self.dt, self.d, self.cos.data_ptr(), self.sin.data_ptr(),
-                                             self.cos.shape[0], int(kv_len), int(pos_q), _stream()), "spatten_step_set")
+    def _per_seq(self, x, what):
+        """ints / sequences / int32 device tensors of length ``batch`` -> an int32 device tensor [batch] (kept alive by the caller)."""
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.int32 or not x.is_cuda or x.dim() != 1 or x.numel() != self.batch or not x.is_contiguous():
+                raise TypeError(f"StepState: {what} must be a contiguous int32 device tensor of length {self.batch}")
+            return x
+        vals = [int(x)] * self.batch if isinstance(x, int) else [int(v) for v in x]
+        if len(vals) != self.batch:
+            raise ValueError(f"StepState: {what} needs one value per sequence ({self.batch})")
+        return torch.tensor(vals, dtype=torch.int32).to(self.buf.device)
 
-    def advance(self, delta: int = 1):
-        _lib.check(self.lib.spatten_step_advance(self.buf.data_ptr(), self.dt, self.d, self.cos.data_ptr(), self.sin.data_ptr(),
-                                                 self.cos.shape[0], int(delta), _stream()), "spatten_step_advance")
+    def set(self, kv_len, pos_q):
+        """Values -> state.  ``kv_len`` = the current cache length; after the next ``advance()`` the state describes the step that
+        appends row ``kv_len``.  Shared state: host ints (not capturable: the values are launch arguments).  ``batch=B``: ints,
+        sequences or int32 device tensors of length B (device tensors: a pure stream operation, capturable)."""
+        if self.batch is None:
+            if max(kv_len, pos_q + 1) > self.cos.shape[0]:
+                raise ValueError("step state beyond the rotary table")
+            _lib.check(self.lib.spatten_step_set(self.buf.data_ptr(), self.dt, self.d, self.cos.data_ptr(), self.sin.data_ptr(),
+                                                 self.cos.shape[0], int(kv_len), int(pos_q), _stream()), "spatten_step_set")
+            return
+        # host values are checked like the scalar call's; device values cannot be (the kernel clamps the rotary rows to the table)
+        for x, extra in ((kv_len, 0), (pos_q, 1)):
+            if not isinstance(x, torch.Tensor):
+                vals = [int(x)] if isinstance(x, int) else [int(v) for v in x]
+                if vals and (min(vals) < 0 or max(vals) + extra > self.cos.shape[0]):
+                    raise ValueError("step state beyond the rotary table")
+        n, pq = self._per_seq(kv_len, "kv_lens"), self._per_seq(pos_q, "pos_q")
+        _lib.check(self.lib.spatten_step_set_batch(self.buf.data_ptr(), self.stride, self.batch, self.dt, self.d, self.cos.data_ptr(),
+                                                   self.sin.data_ptr(), self.cos.shape[0], n.data_ptr(), pq.data_ptr(), _stream()),
+                   "spatten_step_set_batch")
+        self._keep = (n, pq)            # the launch reads them: alive until the next set
+
+    def advance(self, delta: int = 1, deltas=None):
+        """``deltas`` (``batch=B`` only): one step per sequence — an int32 device tensor of length B (capturable) or a host sequence
+        (uploaded first: not inside a capture).  A sequence with delta 0 keeps its state, but a launch still runs it and rewrites
+        row length - 1 from its k_new / v_new: hand it its last rows again."""
+        if self.batch is None:
+            if deltas is not None:
+                raise ValueError("StepState: deltas need a batched state")
+            _lib.check(self.lib.spatten_step_advance(self.buf.data_ptr(), self.dt, self.d, self.cos.data_ptr(), self.sin.data_ptr(),
+                                                     self.cos.shape[0], int(delta), _stream()), "spatten_step_advance")
+            return
+        dl = None if deltas is None else self._per_seq(deltas, "deltas")
+        _lib.check(self.lib.spatten_step_advance_batch(self.buf.data_ptr(), self.stride, self.batch, self.dt, self.d, self.cos.data_ptr(),
+                                                       self.sin.data_ptr(), self.cos.shape[0], int(delta), _ptr(dl), _stream()),
+                   "spatten_step_advance_batch")
+        self._keep_d = dl
 
     def read(self, all_words: bool = False):
-        """(kv_len, pos_q) [, steps since the last set, rows of the previous step's stash] — synchronises; for tests."""
-        w = self.buf[:16].view(torch.int32).cpu()
-        return tuple(int(x) for x in w) if all_words else (int(w[0]), int(w[1]))
+        """(kv_len, pos_q) [, steps since the last set, rows of the previous step's stash] — synchronises; for tests.
+        ``batch=B``: a list of B such tuples."""
+        if self.batch is None:
+            w = self.buf[:16].view(torch.int32).cpu()
+            return tuple(int(x) for x in w) if all_words else (int(w[0]), int(w[1]))
+        w = self.buf.view(self.batch, self.stride)[:, :16].contiguous().view(torch.int32).cpu()
+        return [tuple(int(x) for x in r) if all_words else (int(r[0]), int(r[1])) for r in w]
 
 
 class SlabDecodeCall:
