@@ -159,7 +159,14 @@ typedef struct spatten_decode_args {
   void* workspace; int32_t workspace_splits;
   int32_t batch, heads, kv_heads, head_dim, kv_len, pos_q, n_splits;
   const int32_t* head_ids; int32_t n_active_heads; int32_t flags;
-  const void* prev_scores; int64_t prev_sb, prev_sh; const float* prev_lse; int32_t prev_len; int32_t pad1_;
+  const void* prev_scores; int64_t prev_sb, prev_sh; const float* prev_lse; int32_t prev_len;
+  int32_t acc_sb;                  /* with importance_acc: ELEMENTS between the accumulators of consecutive sequences — sequence b, head h,
+                                      key j adds into importance_acc[b * acc_sb + h * acc_sh + j] (acc [B, H, >= rows]: exactly one add per
+                                      entry per step, deterministic at any batch).  0 = ONE accumulator [H, >= rows] shared by the batch.
+                                      > 0 is what a per-sequence state (step_state_sb != 0) needs to accumulate; also admitted in the
+                                      static launch and with the shared state.  < 0, or != 0 without importance_acc:
+                                      SPATTEN_ERR_INVALID; with pq_*: SPATTEN_ERR_UNSUPPORTED.  (The block's former pad word: callers
+                                      zero-fill the block, its size and offsets stand.) */
   float* importance_acc; int64_t acc_sh;
   float* head_abs_acc;
   const void* pq_msb; const void* pq_lsb; const float* pq_scale;
@@ -323,8 +330,12 @@ int spatten_attn_decode_chain(const spatten_chain_args_t* args, void* stream);
  * matrix-core grouped-query form), the captured graph, the per-sequence append slot and position, and no mask tensor.
  * Served by every route of the plain step (per-query-head and grouped-query kernels, all dtypes and head dims); head_ids,
  * head_abs_acc, SPATTEN_DECODE_GROUPED_HEADS, scores, lse, k_new / v_new and proj_* are admitted as with one state; mask,
- * position_ids and SCORES_ONLY stay refused.  SPATTEN_ERR_UNSUPPORTED with importance_acc (the accumulator [H, L] has no batch
- * axis: fold a sequence's stash and lse with spatten_importance_accumulate on a slice), pq_* and qkv_*.  The chained launch, the
+ * position_ids and SCORES_ONLY stay refused.  importance_acc (the fused cascade accumulation) needs an accumulator with a batch axis:
+ * acc_sb > 0, sequence b folds the rows its OWN previous step wrote (its state word 3) into importance_acc + b * acc_sb — one add per
+ * entry per step; with acc_sb == 0 the step is refused with SPATTEN_ERR_UNSUPPORTED (one [H, L] accumulator cannot take sequences of
+ * different lengths).  The turn's last step is folded by spatten_importance_accumulate_step, the batch is pruned by
+ * spatten_prune_ragged, and spatten_step_set_batch takes the new lengths: no host value of a length anywhere.
+ * SPATTEN_ERR_UNSUPPORTED with pq_* and qkv_*.  The chained launch, the
  * profiled-plane / local-V entry points and spatten_kv_append_step keep the one shared state.
  * ---------------------------------------------------------------------------------------------- */
 size_t spatten_step_state_bytes(int dtype, int head_dim);
@@ -496,6 +507,57 @@ int spatten_prune_layers_scored(int score_dtype, int kv_dtype, int layers,
                                 int lo, int hi, int k, int tail_lo, int tail_len, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ragged prune event: the prune event of a batch whose sequences differ in length (one step state per sequence, above), ALL layers
+ * and ALL sequences in at most three launches on `stream` — select, K/V gather + rotated shadow, accumulator gather.  No allocation,
+ * no synchronisation, no host value of a length: capturable.  Zero-fill the block and set struct_size (strict equality).
+ *   lens / lens_step   DEVICE int32: the live rows of sequence b at lens[b * lens_step] — 1: a dense array; step_state_sb / 4: word 0
+ *                      of a step-state array, read in place.  Values are clamped to [0, bound].
+ *   bound              host: >= every length, <= the rows of the source planes, score rows and source accumulators; sizes windows
+ *                      and grids
+ *   start, recent, k, num_coming   host: the reference's start_size / recent_size / important_size and the tokens about to come
+ *                      (kv_cache_token_pruning.py:46,59,80-82); start >= 0, k > 0, 0 <= num_coming <= recent
+ *   score_ptrs         device table [layers] -> [batch, heads, >= bound] in score_dtype (rows contiguous)
+ *   k_src_ptrs, v_src_ptrs, k_dst_ptrs, v_dst_ptrs, kr_dst_ptrs (optional)   device tables as in spatten_prune_layers_scored; `heads`
+ *                      = the heads of the cache planes (KV heads); row pitch head_dim; source and destination are DISTINCT buffers
+ *   cos, sin, table_rows   rotary half tables, table_rows >= out_rows: required with kr_dst_ptrs
+ *   out_rows           rows of every destination plane the event defines: >= keep_rows = start + k + recent - num_coming, <= the
+ *                      destination capacity
+ *   idx                int32 [layers, batch, heads, k] out (contiguous)
+ *   acc_src_ptrs, acc_dst_ptrs   both or neither -> fp32 [batch, acc_heads, cols]; acc_heads a multiple of heads: accumulator row a
+ *                      follows KV head a / (acc_heads / heads) (a grouped-query model keeps one row per query head over the per-KV-head
+ *                      row map; the caller supplies group-summed scores)
+ *   acc_cols           >= keep_rows: columns of every destination accumulator row the event defines
+ *   new_lens           int32 [batch] out
+ * Sequence b with len_b + num_coming > start + k + recent is pruned: window [start, hi_b), hi_b = len_b - recent + num_coming; the k
+ * largest are kept (ties at the k-th value: lowest index first, NaN ranks largest; the bits of spatten_topk_select(start, hi_b, k));
+ * row map [0, start) | idx | [hi_b, len_b); new_len_b = keep_rows.  Any other sequence keeps the identity map, new_len_b = len_b (<=
+ * keep_rows), and its idx rows are left untouched.  K / V rows [0, new_len_b) of every layer move through the map, shadow row r = new
+ * K row r rotated at position r (spatten_kv_compact's arithmetic), accumulator entries move through the same map; rows
+ * [new_len_b, out_rows) of K, V and the shadow and accumulator columns [new_len_b, acc_cols) are written as ZERO (the device-length
+ * step needs finite rows past the length; a key appended later starts from 0).  A length of 0 yields all zeros.
+ * Every refusal is host arithmetic before the first launch, with spatten_prune_layers_scored's codes: SPATTEN_ERR_INVALID for NULL
+ * pointers, a wrong struct_size or a value outside the ranges above; SPATTEN_ERR_UNSUPPORTED for head_dim * element size not a multiple
+ * of 32 bytes and for grids beyond the launch limits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct spatten_prune_ragged_args {
+  uint32_t struct_size;            /* sizeof(spatten_prune_ragged_args_t) of the caller */
+  int32_t score_dtype, kv_dtype;
+  int32_t layers, batch, heads, head_dim;
+  int32_t lens_step;
+  const int32_t* lens;
+  int32_t bound, start, recent, k, num_coming, out_rows, table_rows, acc_heads, acc_cols, pad0_;
+  const void* const* score_ptrs; int64_t score_batch_stride, score_head_stride;
+  const void* const* k_src_ptrs; const void* const* v_src_ptrs; int64_t src_batch_stride, src_head_stride;
+  void* const* k_dst_ptrs; void* const* v_dst_ptrs; void* const* kr_dst_ptrs; int64_t dst_batch_stride, dst_head_stride;
+  const void* cos; const void* sin;
+  int32_t* idx;
+  const float* const* acc_src_ptrs; int64_t acc_src_batch_stride, acc_src_head_stride;
+  float* const* acc_dst_ptrs; int64_t acc_dst_batch_stride, acc_dst_head_stride;
+  int32_t* new_lens;
+} spatten_prune_ragged_args_t;
+int spatten_prune_ragged(const spatten_prune_ragged_args_t* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * SpAtten semantics with no numeric implementation in the reference ("parity unpinned": restated from the RTL
  * control flow / README, checked against oracle/spatten_oracle.py only).
  * ---------------------------------------------------------------------------------------------- */
@@ -508,6 +570,20 @@ int spatten_importance_accumulate(int dtype, const void* stash, int64_t sb, int6
                                   const float* lse, const void* mask, int64_t mask_sb, int64_t mask_sq,
                                   float* acc, int64_t acc_sh, int batch, int heads, int q_len, int kv_len,
                                   int causal, void* stream);
+/* The fold of the PENDING step of a device-length batch: a captured turn ends with one step whose probabilities no later step
+ * folds, and the host knows neither which of the two swapping buffers holds it nor how many rows it has.  stash0 / lse0 and stash1 /
+ * lse1 are the two buffers in the order the decode step takes `scores` / `lse` and `prev_scores` / `prev_lse` (stash [B,H,>=bound],
+ * common strides, rows contiguous; lse [B,H,2] fp32 dense).  Sequence b, with words (n, ., cnt, .) of its state at step_state + b *
+ * step_state_sb: cnt == 0 (no step since the set): nothing; otherwise buffer (cnt - 1) & 1 and, for j < min(n, bound),
+ *   acc[b * acc_batch_stride + h * acc_head_stride + j] += exp(s - (m == -inf ? 0 : m)) / l
+ * — spatten_importance_accumulate's expression for one row, one add per entry: on sequence b's slice with kv_len = n it leaves the
+ * bits that call leaves.  One launch, no host value of a length: capturable.  step_state_sb == 0: one state for the whole batch.
+ * SPATTEN_ERR_INVALID: NULL pointers, batch / heads / bound <= 0, negative strides of acc, acc_batch_stride == 0 with batch > 1, a
+ * step_state_sb that is negative or no multiple of 4. */
+int spatten_importance_accumulate_step(int dtype, const void* stash0, const float* lse0, const void* stash1, const float* lse1,
+                                       int64_t stash_batch_stride, int64_t stash_head_stride,
+                                       float* acc, int64_t acc_batch_stride, int64_t acc_head_stride,
+                                       int batch, int heads, int bound, const void* step_state, int step_state_sb, void* stream);
 /* The same accumulation for a multi-token forward WITHOUT the [B,H,q,N] stash (4 GiB per layer at q = N = 8192): the
  * logits are recomputed on the matrix cores from q (un-rotated, rotated here like spatten_attn_prefill does) and the
  * rotated shadow, with the flash kernel's roundings, and turned into probabilities with the row statistics `lse`

@@ -31,7 +31,7 @@ class DecodeArgs(ctypes.Structure):
         ("pos_q", c_int32), ("n_splits", c_int32),
         ("head_ids", c_void_p), ("n_active_heads", c_int32), ("flags", c_int32),
         ("prev_scores", c_void_p), ("prev_sb", c_int64), ("prev_sh", c_int64), ("prev_lse", c_void_p),
-        ("prev_len", c_int32), ("pad1_", c_int32),
+        ("prev_len", c_int32), ("acc_sb", c_int32),
         ("importance_acc", c_void_p), ("acc_sh", c_int64),
         ("head_abs_acc", c_void_p),
         ("pq_msb", c_void_p), ("pq_lsb", c_void_p), ("pq_scale", c_void_p),
@@ -44,6 +44,27 @@ class DecodeArgs(ctypes.Structure):
         ("qkv_x", c_void_p), ("qkv_weight", c_void_p), ("qkv_w_sn", c_int64), ("qkv_bias", c_void_p),
         ("qkv_exchange", c_void_p), ("qkv_hidden", c_int32), ("pad5_", c_int32),
     ]
+
+class PruneRaggedArgs(ctypes.Structure):
+    """``spatten_prune_ragged_args_t`` (include/spatten.h): the argument block of ``spatten_prune_ragged``."""
+    _fields_ = [
+        ("struct_size", c_uint32), ("score_dtype", c_int32), ("kv_dtype", c_int32),
+        ("layers", c_int32), ("batch", c_int32), ("heads", c_int32), ("head_dim", c_int32),
+        ("lens_step", c_int32),
+        ("lens", c_void_p),
+        ("bound", c_int32), ("start", c_int32), ("recent", c_int32), ("k", c_int32), ("num_coming", c_int32),
+        ("out_rows", c_int32), ("table_rows", c_int32), ("acc_heads", c_int32), ("acc_cols", c_int32), ("pad0_", c_int32),
+        ("score_ptrs", c_void_p), ("score_batch_stride", c_int64), ("score_head_stride", c_int64),
+        ("k_src_ptrs", c_void_p), ("v_src_ptrs", c_void_p), ("src_batch_stride", c_int64), ("src_head_stride", c_int64),
+        ("k_dst_ptrs", c_void_p), ("v_dst_ptrs", c_void_p), ("kr_dst_ptrs", c_void_p),
+        ("dst_batch_stride", c_int64), ("dst_head_stride", c_int64),
+        ("cos", c_void_p), ("sin", c_void_p),
+        ("idx", c_void_p),
+        ("acc_src_ptrs", c_void_p), ("acc_src_batch_stride", c_int64), ("acc_src_head_stride", c_int64),
+        ("acc_dst_ptrs", c_void_p), ("acc_dst_batch_stride", c_int64), ("acc_dst_head_stride", c_int64),
+        ("new_lens", c_void_p),
+    ]
+
 
 class ChainLayer(ctypes.Structure):
     """``spatten_chain_layer_t`` (include/spatten.h, ABI 5): one entry of the DEVICE table of a chained decode launch."""
@@ -197,6 +218,10 @@ def _declare(lib):
     lib.spatten_kv_append_step.argtypes = [i, p, p, i64, i64, p, p, p, i64, i64, p, p, p, i64, i64, i64, i64, i, i, i, i, p, p]
     lib.spatten_importance_accumulate.restype = c_int
     lib.spatten_importance_accumulate.argtypes = [i, p, i64, i64, i64, p, p, i64, i64, p, i64, i, i, i, i, i, p]
+    lib.spatten_importance_accumulate_step.restype = c_int
+    lib.spatten_importance_accumulate_step.argtypes = [i, p, p, p, p, i64, i64, p, i64, i64, i, i, i, p, i, p]
+    lib.spatten_prune_ragged.restype = c_int
+    lib.spatten_prune_ragged.argtypes = [POINTER(PruneRaggedArgs), p]
     lib.spatten_row_lse.restype = c_int
     lib.spatten_row_lse.argtypes = [i, p, i64, i64, i64, p, i64, i64, p, i, i, i, i, i, p]
     lib.spatten_importance_compact.restype = c_int

@@ -66,6 +66,29 @@ __global__ __launch_bounds__(256) void importance_accumulate_kernel(const T* __r
   acc[h * acc_sh + j] += a;
 }
 
+// The pending step of a device-length batch (spatten_importance_accumulate_step): sequence b's state words (n, ., cnt, .) say which of
+// the two swapping buffers its last step wrote — (cnt - 1) & 1 — and how many rows; importance_accumulate_kernel's expression for
+// that one row, one add per entry.  Nothing read or written depends on a length beyond min(n, bound).
+template <typename T>
+__global__ __launch_bounds__(256) void importance_accumulate_step_kernel(const T* __restrict__ stash0, const float* __restrict__ lse0,
+                                                                         const T* __restrict__ stash1, const float* __restrict__ lse1,
+                                                                         int64_t sb, int64_t sh, float* __restrict__ acc, int64_t acc_sb,
+                                                                         int64_t acc_sh, int H, int bound, const char* __restrict__ step,
+                                                                         int step_sb) {
+  const int j = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int32_t* st = reinterpret_cast<const int32_t*>(step + (int64_t)b * step_sb);
+  const int n = min(st[0], bound), cnt = st[2];
+  if (cnt == 0 || j >= n) return;
+  const bool odd = ((cnt - 1) & 1) != 0;
+  const T* stash = odd ? stash1 : stash0;
+  const float* ml = (odd ? lse1 : lse0) + (int64_t)(b * H + h) * 2;
+  float a = 0.f;
+  const float s = DT<T>::to_f32(stash[b * sb + h * sh + j]);
+  const float mu = (ml[0] == -INFINITY) ? 0.f : ml[0];
+  a += __expf(s - mu) / ml[1];
+  acc[b * acc_sb + h * acc_sh + j] += a;
+}
+
 __global__ __launch_bounds__(256) void importance_compact_kernel(const float* __restrict__ src, int64_t src_sh,
                                                                  float* __restrict__ dst, int64_t dst_sh,
                                                                  const int32_t* __restrict__ idx, int64_t idx_sh,
@@ -287,6 +310,23 @@ extern "C" int spatten_importance_accumulate(int dtype, const void* stash, int64
   SPATTEN_BY_DTYPE(dtype, hipLaunchKernelGGL((importance_accumulate_kernel<T>), grid, dim3(256), 0, st, (const T*)stash, sb, sh,
                                              sq, lse, (const T*)mask, mask_sb, mask_sq, acc, acc_sh, batch, heads, q_len,
                                              kv_len, causal));
+  return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
+}
+
+extern "C" int spatten_importance_accumulate_step(int dtype, const void* stash0, const float* lse0, const void* stash1,
+                                                  const float* lse1, int64_t stash_batch_stride, int64_t stash_head_stride, float* acc,
+                                                  int64_t acc_batch_stride, int64_t acc_head_stride, int batch, int heads, int bound,
+                                                  const void* step_state, int step_state_sb, void* stream) {
+  if (!ok_dtype(dtype) || !stash0 || !lse0 || !stash1 || !lse1 || !acc || !step_state || batch <= 0 || heads <= 0 || bound <= 0)
+    return SPATTEN_ERR_INVALID;
+  if (acc_batch_stride < 0 || acc_head_stride < 0 || (batch > 1 && acc_batch_stride == 0)) return SPATTEN_ERR_INVALID;
+  if (step_state_sb < 0 || step_state_sb % 4 != 0) return SPATTEN_ERR_INVALID;
+  if (heads > 65535 || batch > 65535) return SPATTEN_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)ceil_div(bound, 256), (unsigned)heads, (unsigned)batch);
+  SPATTEN_BY_DTYPE(dtype, hipLaunchKernelGGL((importance_accumulate_step_kernel<T>), grid, dim3(256), 0, st, (const T*)stash0, lse0,
+                                             (const T*)stash1, lse1, stash_batch_stride, stash_head_stride, acc, acc_batch_stride,
+                                             acc_head_stride, heads, bound, (const char*)step_state, step_state_sb));
   return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
 }
 

@@ -455,6 +455,7 @@ struct DecodeCall {
   // cascade importance, deferred by one step: the PREVIOUS step's stash + (max, sum) are folded into acc by this launch
   const void* prev_scores = nullptr; int64_t pv_sb = 0, pv_sh = 0; const float* prev_lse = nullptr;
   float* acc = nullptr; int64_t acc_sh = 0; int prev_len = 0;
+  int acc_sb = 0;              // elements between the accumulators of consecutive sequences (spatten_decode_args_t::acc_sb; 0: one for the batch)
   float* head_abs = nullptr;   // [B*H] head importance accumulators (n_q == 1 only)
   const void* step = nullptr;  // device-resident step state (step.hip): kv_len above is then a bound
   int step_sb = 0;             // bytes between the states of consecutive sequences (spatten_decode_args_t::step_state_sb; 0: one state)

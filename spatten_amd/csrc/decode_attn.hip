@@ -515,12 +515,15 @@ static int decode_rows_check(const DecodeCall& c, int& n_active, int& S, int& ch
   // roles every step (same strides, rows up to the bound)
   if (c.step && c.acc && (!c.scores || !c.lse || !c.prev_scores || !c.prev_lse || c.pv_sb != c.sc_sb || c.pv_sh != c.sc_sh))
     return SPATTEN_ERR_INVALID;
-  // one state per sequence (a ragged batch): whole 256-byte lines apart, no two states overlapping.  The accumulator [H, L] has no
-  // batch axis, the quantised-key passes and the fused projections keep the shared state.
+  // an accumulator per sequence (acc_sb: elements between them): not in the quantised-key passes, which keep their own argument
+  if (c.acc_sb < 0 || (c.acc_sb != 0 && !c.acc)) return SPATTEN_ERR_INVALID;
+  if (c.acc_sb != 0 && pq) return SPATTEN_ERR_UNSUPPORTED;
+  // one state per sequence (a ragged batch): whole 256-byte lines apart, no two states overlapping.  One accumulator [H, L] without
+  // a batch axis cannot take sequences of different lengths; the quantised-key passes and the fused projections keep the shared state.
   if (c.step_sb != 0) {
     if (!c.step || c.step_sb % 256 != 0 || c.step_sb < 0 || (size_t)c.step_sb < spatten_step_state_bytes(c.dtype, c.head_dim))
       return SPATTEN_ERR_INVALID;
-    if (c.acc || pq || c.qkv_x) return SPATTEN_ERR_UNSUPPORTED;
+    if ((c.acc && c.acc_sb == 0) || pq || c.qkv_x) return SPATTEN_ERR_UNSUPPORTED;
   }
   if (c.head_dim != 64 && c.head_dim != 128 && c.head_dim != 256) return SPATTEN_ERR_UNSUPPORTED;
   if (c.dtype != SPATTEN_F32 && c.dtype != SPATTEN_F16 && c.dtype != SPATTEN_BF16) return SPATTEN_ERR_INVALID;
@@ -613,6 +616,7 @@ int decode_rows(const DecodeCall& c, hipStream_t stream) {
   p.pq_thr = pq ? pq->threshold : 0.f; p.pq_need = pq ? pq->need : nullptr;                              \
   p.prev_scores = (const T*)c.prev_scores; p.pv_sb = c.pv_sb; p.pv_sh = c.pv_sh; p.prev_lse = c.prev_lse; \
   p.acc = (c.prev_len > 0 || c.step) ? c.acc : nullptr; p.acc_sh = c.acc_sh; p.prev_len = c.prev_len;   \
+  p.acc_sb = c.acc_sb;                                                                                   \
   p.head_abs = c.head_abs;                                                                               \
   p.ws_err = (unsigned*)c.workspace;                                                                     \
   p.ws_cnt = c.workspace ? (unsigned*)((char*)c.workspace + kDecodeWsHeader) : (unsigned*)c.cos;         \
@@ -701,7 +705,7 @@ static int decode_call_of(const spatten_decode_args_t* a, DecodeCall& c, PQKeys&
   c.pos_q = a->pos_q; c.n_q = 1; c.causal = 0; c.n_splits = a->n_splits;
   c.head_ids = a->head_ids; c.n_active = a->n_active_heads; c.flags = a->flags;
   c.prev_scores = a->prev_scores; c.pv_sb = a->prev_sb; c.pv_sh = a->prev_sh; c.prev_lse = a->prev_lse;
-  c.acc = a->importance_acc; c.acc_sh = a->acc_sh; c.prev_len = a->prev_len;
+  c.acc = a->importance_acc; c.acc_sh = a->acc_sh; c.acc_sb = a->acc_sb; c.prev_len = a->prev_len;
   c.head_abs = a->head_abs_acc;
   c.step = a->step_state; c.step_sb = a->step_state_sb; c.layout_len = a->kv_len_layout;
   c.proj_w = a->proj_weight; c.proj_w_sn = a->proj_w_sn; c.proj_bias = a->proj_bias; c.proj_out = a->proj_out;

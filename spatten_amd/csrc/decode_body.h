@@ -67,6 +67,7 @@ struct DecodeParams {
   float pq_thr; int32_t* pq_need;   // [B*H]: written by the MSB pass (max prob < thr), read by the refetch pass
   // cascade importance (CASC): the previous step's stash + (max, sum) folded into acc while this step's keys stream
   const T* prev_scores; int64_t pv_sb, pv_sh; const float* prev_lse; float* acc; int64_t acc_sh; int prev_len;
+  int acc_sb = 0;       // CASC: elements between the accumulators of consecutive sequences (0: one [H, rows] accumulator for the batch)
   float* head_abs;      // optional [B*H]: += sum_e |out[b, h, e]| (head importance, README.md:21), by the unit's last writer
   const int32_t* step;  // DYN: the device-resident step state (step.hip): word 0 = the cache length AFTER this step's append.
                         // N below is then only a BOUND (grid / chunk / load addresses come from it); cos / sin point at the
@@ -488,7 +489,7 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
     const float pm = odd ? ml_b[0] : ml_a[0], pl = odd ? ml_b[1] : ml_a[1];
     casc_m = (pm == -INFINITY) ? 0.f : pm;
     casc_rl = 1.0f / pl;
-    accp = p.acc + h * p.acc_sh;
+    accp = p.acc + (int64_t)b * p.acc_sb + h * p.acc_sh;
   }
 
   // per-THREAD online softmax (the LPR lanes of a row share its score, so they agree): no barrier and

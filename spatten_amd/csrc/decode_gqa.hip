@@ -72,6 +72,7 @@ struct GqaParams {
   // CASC (cascade importance, deferred by one step: decode_body.h): the previous step's stash + (max, sum) folded into acc [H, >= N]
   // (behind the plain step's arguments: their offsets are those of the instantiations without the fold)
   const T* prev_scores; int64_t pv_sb, pv_sh; float* prev_lse; float* acc; int64_t acc_sh; int prev_len;
+  int acc_sb = 0;                                           // CASC: elements between the accumulators of consecutive sequences (0: one for the batch)
   // HL (head pruning): the ascending device list of kept heads (nullptr: all), its length, the head importance accumulator [B * H]
   const int32_t* head_ids; int n_active; float* head_abs;
 };
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(256, 1) void decode_gqa_kernel(const GqaParams<T> p
     casc_rl = 1.0f / pl;
 #pragma unroll
     for (int e = 0; e < 4; ++e) tail[e] = (DYN && odd) ? tail_b[e] : tail_a[e];
-    accp = p.acc + (int64_t)(hkv * G + min(col, G - 1)) * p.acc_sh;
+    accp = p.acc + (int64_t)b * p.acc_sb + (int64_t)(hkv * G + min(col, G - 1)) * p.acc_sh;
   }
   float m_run = -INFINITY, l_run = 0.f;
   f32x16 o[DB];
@@ -799,6 +800,8 @@ bool decode_gqa_plan(const DecodeCall& c, int& S, int& chunk32) {
   const int G = c.heads / c.kv_heads;
   if (G > 32 || c.lse_q > 1) return false;
   if (!c.acc && c.prev_scores) return false;
+  // an accumulator with a batch axis (acc_sb > 0) is what one state per sequence needs to accumulate: decode_rows_check's rule
+  if (c.acc_sb < 0 || (c.acc_sb != 0 && !c.acc) || (c.step_sb != 0 && c.acc && c.acc_sb == 0)) return false;
   if (c.acc) {
     // the previous stash rows come by 16-byte LDS-DMA pieces through a 32-bit descriptor over the group's rows; a layout that does
     // not fit takes the per-query-head kernel.  Default mode: no accumulation step has measured faster in this form yet (DESIGN.md
@@ -858,7 +861,7 @@ int decode_gqa_rows(const DecodeCall& c, hipStream_t stream) {
   if (p.sc_vec && (uintptr_t)c.scores % 16 == 0 && c.sc_sb % 8 == 0 && c.sc_sh % 8 == 0 && sizeof(T) == 2) p.sc_vec = 2; \
   p.lse = c.lse;                                                                                                 \
   p.prev_scores = (const T*)c.prev_scores; p.pv_sb = c.pv_sb; p.pv_sh = c.pv_sh; p.prev_lse = (float*)c.prev_lse;  \
-  p.acc = c.acc; p.acc_sh = c.acc_sh; p.prev_len = c.prev_len;                                                   \
+  p.acc = c.acc; p.acc_sh = c.acc_sh; p.acc_sb = c.acc_sb; p.prev_len = c.prev_len;                              \
   p.head_ids = c.head_ids; p.n_active = c.head_ids ? c.n_active : 0; p.head_abs = c.head_abs;                    \
   p.ws_err = (unsigned*)c.workspace;                                                                             \
   p.ws_cnt = c.workspace ? (unsigned*)((char*)c.workspace + kDecodeWsHeader) : nullptr;                          \

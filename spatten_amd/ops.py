@@ -177,6 +177,7 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     traffic (pass 1 of local V pruning).
     cascade = (acc [H,>=prev_len] fp32, prev_scores [B,H,>=prev_len], prev_lse [B,H,2], prev_len): the PREVIOUS decode
     step's softmax probabilities are added to acc while this step streams (cumulative importance, no extra launch).
+    acc [B,H,>=prev_len]: one accumulator per sequence (spatten_decode_args_t::acc_sb) — what a per-sequence ``step`` needs.
     With ``step``: scores / lse and prev_scores / prev_lse are the two buffers that swap roles every step (prev_len unused).
     pq = (PQPlanes, threshold, need_lsb int32 [B*H]): keys come from the progressive-quantisation planes (MSB pass,
     LSB refetch for heads whose max probability is below threshold) instead of kr_cache.
@@ -184,7 +185,7 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     layout: lay the split-N decomposition out for this length (>= kv_len) instead of kv_len.
     step (StepState): the device-resident length — ``kv_len`` is then the BOUND of the launch, ``pos_q`` is not read, rows
     [length, bound) of kr_cache / v_cache must hold finite values.  ``StepState(..., batch=B)``: a ragged batch — sequence b has
-    its own length, query position and append slot (the launch still streams the bound per sequence); not with cascade / pq.
+    its own length, query position and append slot (the launch still streams the bound per sequence); cascade needs a 3-D acc; not with pq.
     proj = (weight [N, H*d], bias [N] or None, proj_out [B, N]): the step's output projection (modify_llama.py:163) issued by
     the same C call (a second launch of spatten_gemv's kernel: one host call per layer-step); ``proj_out`` is filled.
     gqa_form: build the argument block, launch NOTHING and return whether the call would run in the matrix-core grouped-query
@@ -261,10 +262,14 @@ def attn_decode(q: torch.Tensor, k_cache: Optional[torch.Tensor], kr_cache: Opti
     if cascade is not None:
         acc, prev_scores, prev_lse, prev_len = cascade
         _dev(acc, prev_scores, prev_lse)
-        if acc.dtype != torch.float32 or acc.stride(1) != 1 or acc.shape[0] != H or acc.shape[1] < prev_len \
+        if acc.dim() not in (2, 3) or acc.dtype != torch.float32 or acc.stride(-1) != 1 or acc.shape[-2] != H or acc.shape[-1] < prev_len \
+                or (acc.dim() == 3 and (acc.shape[0] != B or (B > 1 and acc.stride(0) <= 0) or acc.stride(0) >= 2 ** 31)) \
                 or prev_scores.stride(-1) != 1 or prev_lse.dtype != torch.float32 or not prev_lse.is_contiguous():
-            raise ValueError("cascade: acc fp32 [H, >=prev_len], prev_scores [B,H,>=prev_len] rows contiguous, prev_lse [B,H,2]")
-        a.importance_acc, a.acc_sh = acc.data_ptr(), acc.stride(0)
+            raise ValueError("cascade: acc fp32 [H, >=prev_len] or [B, H, >=prev_len], prev_scores [B,H,>=prev_len] rows contiguous, "
+                             "prev_lse [B,H,2]")
+        a.importance_acc, a.acc_sh = acc.data_ptr(), acc.stride(-2)
+        if acc.dim() == 3:      # one accumulator per sequence: exactly one add per entry per step (B = 1: the stride is never applied)
+            a.acc_sb = acc.stride(0) if B > 1 else max(acc.stride(0), 1)
         a.prev_scores, a.prev_sb, a.prev_sh = prev_scores.data_ptr(), prev_scores.stride(0), prev_scores.stride(1)
         a.prev_lse, a.prev_len = prev_lse.data_ptr(), prev_len
     if head_abs is not None:
@@ -560,6 +565,12 @@ class StepState:
                                                        self.sin.data_ptr(), self.cos.shape[0], int(delta), _ptr(dl), _stream()),
                    "spatten_step_advance_batch")
         self._keep_d = dl
+
+    def lengths(self) -> torch.Tensor:
+        """The strided int32 view of word 0 of every state — the live lengths, read IN PLACE (no copy, no sync): ``lens`` of
+        ``prune_ragged``.  Shape [batch] (1 for the shared state), stride ``stride / 4`` elements."""
+        words = self.buf.view(torch.int32)
+        return words.as_strided((self.batch or 1,), (max(self.stride // 4, 1),))
 
     def read(self, all_words: bool = False):
         """(kv_len, pos_q) [, steps since the last set, rows of the previous step's stash] — synchronises; for tests.
@@ -1070,6 +1081,88 @@ def prune_layers(scores: Sequence[torch.Tensor], Ks: Sequence[torch.Tensor], Vs:
             None if Krd is None else [x[:, :, :Lp] for x in Krd], idx)
 
 
+def prune_ragged(scores: Sequence[torch.Tensor], Ks: Sequence[torch.Tensor], Vs: Sequence[torch.Tensor], lens: torch.Tensor,
+                 bound: int, start: int, recent: int, k: int, num_coming: int, capacity: int,
+                 rope: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                 acc: Optional[Sequence[torch.Tensor]] = None, out_rows: Optional[int] = None, acc_cols: Optional[int] = None,
+                 dst: Optional[tuple] = None, idx: Optional[torch.Tensor] = None, new_lens: Optional[torch.Tensor] = None,
+                 acc_dst: Optional[Sequence[torch.Tensor]] = None, plan: Optional[PrunePlan] = None):
+    """The prune event of a ragged batch (spatten_prune_ragged): every sequence by the reference's rule at its own length, all layers
+    and sequences in at most three launches, no host value of a length (capturable when ``dst`` / ``idx`` / ``new_lens`` / ``acc_dst`` /
+    ``plan`` are handed in: nothing is then allocated or uploaded).
+    scores[l] [B, Hkv, >=bound] (model dtype or fp32); Ks[l] / Vs[l] [B, Hkv, >=bound, d]; lens: int32 DEVICE lengths, 1-D with any
+    element stride (``StepState.lengths()`` reads the states in place); acc[l] fp32 [B, acc_heads, >=bound] follow the rows.
+    Destinations have ``capacity`` rows, of which rows [0, out_rows) (default: all) are defined: moved rows, then ZEROS; likewise
+    columns [0, acc_cols) (default: capacity) of the new accumulators.
+    Returns (Kn, Vn, Krn or None, idx [layers, B, Hkv, k], new_lens int32 [B], new_accs or None)."""
+    _dev(*scores, *Ks, *Vs, lens)
+    lib = _lib.load()
+    nl = len(Ks)
+    B, H, _, d = Ks[0].shape
+    dev = Ks[0].device
+    keep_rows = start + k + recent - num_coming
+    out_rows = int(capacity if out_rows is None else out_rows)
+    if lens.dtype != torch.int32 or lens.dim() != 1 or lens.numel() != B or (B > 1 and lens.stride(0) <= 0):
+        raise TypeError("lens must be a 1-D int32 device tensor with one entry per sequence")
+    if out_rows > capacity or capacity < keep_rows:
+        raise ValueError("prune_ragged: capacity must hold out_rows >= start + k + recent - num_coming")
+    if dst is None:
+        Kd = [torch.empty(B, H, capacity, d, dtype=Ks[0].dtype, device=dev) for _ in range(nl)]
+        Vd = [torch.empty_like(x) for x in Kd]
+        Krd = [torch.empty_like(x) for x in Kd] if rope is not None else None
+    else:
+        Kd, Vd, Krd = dst
+    for t in list(Ks) + list(Vs) + list(Kd) + list(Vd) + list(Krd or []):
+        if t.stride(3) != 1 or t.stride(2) != d:
+            raise ValueError("K/V need contiguous rows (pitch d)")
+    if any(t.stride() != Ks[0].stride() or t.shape[2] < bound for t in list(Ks) + list(Vs)) \
+            or any(t.stride() != Kd[0].stride() or t.shape[2] < out_rows for t in list(Kd) + list(Vd) + list(Krd or [])):
+        raise ValueError("all layers must share strides; sources hold the bound, destinations out_rows")
+    if any(s.dim() != 3 or s.stride(2) != 1 or s.stride() != scores[0].stride() or s.shape[2] < bound or s.dtype != scores[0].dtype
+           for s in scores):
+        raise ValueError("scores need [B, Hkv, >=bound] with contiguous rows and common strides")
+    if Krd is not None and rope is None:
+        raise ValueError("a shadow destination needs the rotary tables")
+    new_accs = None
+    if acc is not None:
+        a_src = list(acc)
+        ah = a_src[0].shape[1]
+        acc_cols = int(capacity if acc_cols is None else acc_cols)
+        new_accs = list(acc_dst) if acc_dst is not None else [torch.empty(B, ah, max(capacity, acc_cols), dtype=torch.float32, device=dev)
+                                                              for _ in range(nl)]
+        for t in a_src + new_accs:
+            if t.dtype != torch.float32 or t.dim() != 3 or t.stride(2) != 1 or t.shape[0] != B or t.shape[1] != ah:
+                raise ValueError("accumulators must be fp32 [B, acc_heads, len] with contiguous rows")
+        if any(t.stride() != a_src[0].stride() or t.shape[2] < bound for t in a_src) \
+                or any(t.stride() != new_accs[0].stride() or t.shape[2] < acc_cols for t in new_accs):
+            raise ValueError("accumulators need common strides and room for the rows")
+    if plan is None:
+        plan = PrunePlan(scores, Ks, Vs, Kd, Vd, Krd, *((a_src, new_accs) if acc is not None else (None, None)))
+    if idx is None:
+        idx = torch.empty(nl, B, H, k, dtype=torch.int32, device=dev)
+    if new_lens is None:
+        new_lens = torch.empty(B, dtype=torch.int32, device=dev)
+    cos, sin = rope if rope is not None else (None, None)
+    a = _lib.PruneRaggedArgs()
+    a.struct_size = ctypes.sizeof(_lib.PruneRaggedArgs)
+    a.score_dtype, a.kv_dtype, a.layers, a.batch, a.heads, a.head_dim = _dt(scores[0]), _dt(Ks[0]), nl, B, H, d
+    a.lens, a.lens_step = lens.data_ptr(), (lens.stride(0) if B > 1 else 1)
+    a.bound, a.start, a.recent, a.k, a.num_coming, a.out_rows = int(bound), int(start), int(recent), int(k), int(num_coming), out_rows
+    a.score_ptrs, a.score_batch_stride, a.score_head_stride = plan.score_ptrs.data_ptr(), scores[0].stride(0), scores[0].stride(1)
+    a.k_src_ptrs, a.v_src_ptrs = plan.ks.data_ptr(), plan.vs.data_ptr()
+    a.src_batch_stride, a.src_head_stride = Ks[0].stride(0), Ks[0].stride(1)
+    a.k_dst_ptrs, a.v_dst_ptrs, a.kr_dst_ptrs = plan.kd.data_ptr(), plan.vd.data_ptr(), _ptr(plan.krd)
+    a.dst_batch_stride, a.dst_head_stride = Kd[0].stride(0), Kd[0].stride(1)
+    a.cos, a.sin, a.table_rows = _ptr(cos), _ptr(sin), (0 if cos is None else cos.shape[0])
+    a.idx, a.new_lens = idx.data_ptr(), new_lens.data_ptr()
+    if acc is not None:
+        a.acc_src_ptrs, a.acc_dst_ptrs, a.acc_heads, a.acc_cols = plan.acc_src.data_ptr(), plan.acc_dst.data_ptr(), ah, acc_cols
+        a.acc_src_batch_stride, a.acc_src_head_stride = a_src[0].stride(0), a_src[0].stride(1)
+        a.acc_dst_batch_stride, a.acc_dst_head_stride = new_accs[0].stride(0), new_accs[0].stride(1)
+    _lib.check(lib.spatten_prune_ragged(ctypes.byref(a), _stream()), "spatten_prune_ragged")
+    return Kd, Vd, Krd, idx, new_lens, new_accs
+
+
 class LayerCascadePlan:
     """Everything ``prune_layer_cascade`` prepares on the host — the per-layer table, the pointer rows, the output buffers — built
     once; ``run()`` issues the event (the C call alone) and returns the same tuple.  For a caller that repeats an event on the
@@ -1190,6 +1283,35 @@ def importance_accumulate(acc: torch.Tensor, stash: torch.Tensor, lse: Optional[
         _ptr(mask), *((0, 0) if mask is None else (mask.stride(0), mask.stride(1))),
         acc.data_ptr(), acc.stride(0), B, H, Q, L, int(causal), _stream())
     _lib.check(rc, "spatten_importance_accumulate")
+    return acc
+
+
+def importance_accumulate_step(acc: torch.Tensor, scores: torch.Tensor, lse: torch.Tensor, prev_scores: torch.Tensor,
+                               prev_lse: torch.Tensor, step: "StepState", bound: int):
+    """Fold the PENDING step of a device-length batch (spatten_importance_accumulate_step): ``scores`` / ``lse`` and ``prev_scores`` /
+    ``prev_lse`` are the two swapping buffers in the order ``attn_decode`` takes them; each sequence's state says which one its last
+    step wrote and how many rows.  acc fp32 [B, H, >=bound] (or [H, >=bound] at B = 1).  One launch, capturable."""
+    _dev(acc, scores, lse, prev_scores, prev_lse)
+    B, H = scores.shape[0], scores.shape[1]
+    if acc.dim() == 2:
+        if B != 1:
+            raise ValueError("importance_accumulate_step: a batch needs acc [B, H, rows]")
+        acc = acc[None]
+    if acc.dtype != torch.float32 or acc.stride(2) != 1 or acc.shape[0] != B or acc.shape[1] != H or acc.shape[2] < bound:
+        raise ValueError("acc must be fp32 [B, H, >=bound] with contiguous rows")
+    if scores.stride(2) != 1 or prev_scores.stride() != scores.stride() or prev_scores.dtype != scores.dtype \
+            or min(scores.shape[2], prev_scores.shape[2]) < bound:
+        raise ValueError("the two stash buffers need contiguous rows up to the bound, one dtype and identical strides")
+    for t in (lse, prev_lse):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B * H * 2:
+            raise ValueError("lse buffers must be contiguous fp32 [B, H, 2]")
+    if (step.batch or 1) != B and step.batch is not None:
+        raise ValueError(f"step state holds {step.batch} sequences, the stash has {B}")
+    rc = _lib.load().spatten_importance_accumulate_step(
+        _dt(scores), scores.data_ptr(), lse.data_ptr(), prev_scores.data_ptr(), prev_lse.data_ptr(), scores.stride(0),
+        scores.stride(1), acc.data_ptr(), acc.stride(0) if B > 1 else 0, acc.stride(1), B, H, int(bound), step.data_ptr(),
+        step.stride, _stream())
+    _lib.check(rc, "spatten_importance_accumulate_step")
     return acc
 
 
