@@ -198,6 +198,18 @@ __device__ inline float xor32_sum(float x) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+// The same sums of TWO values for one swap and no copy (a reduce-scatter step): the swap exchanges a's odd 16-lane rows with
+// b's even ones (permlane32: a's upper half with b's lower half), so the sum of its two results holds a[i] + a[i^16] in the
+// even rows and b[i] + b[i^16] in the odd rows (a[i] + a[i^32] in lanes [0,32), b[i] + b[i^32] in lanes [32,64)) — the
+// same two addends per lane as xor16_sum / xor32_sum, hence the same bits.
+__device__ inline float xor16_pair_sum(float a, float b) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ inline float xor32_pair_sum(float a, float b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
 __device__ inline float xor16_max(float x) {
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));

@@ -696,13 +696,22 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
     for (int i = 0; i < 8; ++i) { olo[i] += dpp_mov<kDppRor8>(olo[i]); ohi[i] += dpp_mov<kDppRor8>(ohi[i]); }
   }
   l_run = xor32_sum(xor16_sum(l_run));
+  // The 16 column sums as a reduce-scatter: a swap exchanges TWO values between the lane halves, so 8 + 4 swaps (no copies)
+  // leave 4 of the 16 sums in each 16-lane row q instead of all 16 in every lane — the same pairing tree (rows 16 apart, then
+  // 32 apart) and the same addends per sum as xor32_sum(xor16_sum(.)), hence the same bits.  Row q holds elements
+  // [4q, 4q + 4) of the lane's 16: q = 0, 1 -> olo[0..4), olo[4..8); q = 2, 3 -> ohi[0..4), ohi[4..8).
+  {
+    float red[4];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { olo[i] = xor32_sum(xor16_sum(olo[i])); ohi[i] = xor32_sum(xor16_sum(ohi[i])); }
-  if (lane < LPR) {
+    for (int j = 0; j < 4; ++j)
+      red[j] = xor32_pair_sum(xor16_pair_sum(olo[j], olo[4 + j]), xor16_pair_sum(ohi[j], ohi[4 + j]));
+    const int q = lane / 16;
+    // one lane per column and row: 4 consecutive elements each.  (A row of s_o is D + 2 floats, so a wave's row is only
+    // 8-byte aligned: no ds_write_b128 — the compiler emits one ds_write2_b64 per lane.)
+    if ((lane & 15) < LPR) {
+      float* dst = &s_o[wave][(q & 2 ? HALF : 0) + 8 * (lane & 15) + 4 * (q & 1)];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      s_o[wave][8 * lane + i] = olo[i];
-      s_o[wave][HALF + 8 * lane + i] = ohi[i];
+      for (int j = 0; j < 4; ++j) dst[j] = red[j];
     }
     if (lane == 0) { s_o[wave][D] = l_run; s_o[wave][D + 1] = m_run; }
   }
@@ -715,12 +724,17 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
   }
   float o_tot = 0.f, l_tot = 0.f;
   {
+    // a valid column of s_o for EVERY thread: those with tid >= D read a duplicate of column tid - D that is thrown away
+    const int te = tid & (D - 1);
     if constexpr (NW == 4) {
       const float m0 = s_o[0][D + 1], m1 = s_o[1][D + 1], m2 = s_o[2][D + 1], m3 = s_o[3][D + 1];
       const float m_wg = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
       const float mu = (m_wg == -INFINITY) ? 0.f : m_wg;
       const float w0 = __expf(m0 - mu), w1 = __expf(m1 - mu), w2 = __expf(m2 - mu), w3 = __expf(m3 - mu);   // exp(-inf) = 0
-      if (tid < D) o_tot = (s_o[0][tid] * w0 + s_o[1][tid] * w1) + (s_o[2][tid] * w2 + s_o[3][tid] * w3);
+      // every thread reads (a valid address in every lane: no exec-masked block, the four reads go out together)
+      const float a0 = s_o[0][te], a1 = s_o[1][te], a2 = s_o[2][te], a3 = s_o[3][te];
+      const float o_all = (a0 * w0 + a1 * w1) + (a2 * w2 + a3 * w3);
+      o_tot = tid < D ? o_all : 0.f;
       l_tot = (s_o[0][D] * w0 + s_o[1][D] * w1) + (s_o[2][D] * w2 + s_o[3][D] * w3);
       m_run = m_wg;
     } else {
@@ -728,12 +742,18 @@ __device__ __forceinline__ void decode_body(const DecodeParams<T>& p, const floa
 #pragma unroll
       for (int w = 0; w < NW; ++w) { mw[w] = s_o[w][D + 1]; m_wg = fmaxf(m_wg, mw[w]); }
       const float mu = (m_wg == -INFINITY) ? 0.f : m_wg;
+      // every thread reads its element of every wave's row (a valid address in every lane), all reads issued before the first
+      // use: ONE LDS round trip instead of one per wave under `if (tid < D)`; the fold order is unchanged
+      float ow[NW], o_all = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) ow[w] = s_o[w][te];
 #pragma unroll
       for (int w = 0; w < NW; ++w) {
         const float ww = __expf(mw[w] - mu);
-        if (tid < D) o_tot = fmaf(s_o[w][tid], ww, o_tot);
+        o_all = fmaf(ow[w], ww, o_all);
         l_tot = fmaf(s_o[w][D], ww, l_tot);
       }
+      o_tot = tid < D ? o_all : 0.f;
       m_run = m_wg;
     }
   }
