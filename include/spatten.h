@@ -335,8 +335,11 @@ int spatten_attn_decode_chain(const spatten_chain_args_t* args, void* stream);
  * entry per step; with acc_sb == 0 the step is refused with SPATTEN_ERR_UNSUPPORTED (one [H, L] accumulator cannot take sequences of
  * different lengths).  The turn's last step is folded by spatten_importance_accumulate_step, the batch is pruned by
  * spatten_prune_ragged, and spatten_step_set_batch takes the new lengths: no host value of a length anywhere.
- * SPATTEN_ERR_UNSUPPORTED with pq_* and qkv_*.  The chained launch, the
- * profiled-plane / local-V entry points and spatten_kv_append_step keep the one shared state.
+ * SPATTEN_ERR_UNSUPPORTED with pq_* and qkv_*.
+ * Over the profiled planes (spatten_pq_decode_args_t::step_state_sb, the same field with the same rule): spatten_attn_decode_pq and
+ * spatten_attn_decode_pq_qint serve one state per sequence, spatten_kv_append_planes_ragged appends for it ("Ragged batch over the
+ * profiled planes" below).  The chained launch, spatten_attn_decode_pq_cascade, spatten_attn_decode_pq_local_v,
+ * spatten_attn_decode_pq_qint_gqa, spatten_pq_pack_planes(step_state) and spatten_kv_append_step keep the one shared state.
  * ---------------------------------------------------------------------------------------------- */
 size_t spatten_step_state_bytes(int dtype, int head_dim);
 /* state := (kv_len, pos_q) from HOST values + the rotary rows of positions pos_q and kv_len - 1 (cos / sin: the half tables
@@ -737,7 +740,8 @@ typedef struct spatten_pq_planes {
 size_t spatten_pq_plane_row_bytes(int head_dim, int bits);
 /* Quantise rows [row_lo, row_hi) of the rotated shadow kr_cache into the key planes and of v_cache into the value plane.
  * With `step_state` (device-resident length, see above) the ONE row (state word 0) - 1 is packed instead — the step's
- * row, after spatten_kv_append_step wrote it — and row_hi is the planes' capacity (a row >= row_hi is not written). */
+ * row, after spatten_kv_append_step wrote it — and row_hi is the planes' capacity (a row >= row_hi is not written).  The state is
+ * the ONE shared state: a ragged batch packs its step rows with spatten_kv_append_planes_ragged or inside spatten_attn_decode_pq. */
 int spatten_pq_pack_planes(int dtype, const void* kr_cache, const void* v_cache, int64_t kv_sb, int64_t kv_sh,
                            const spatten_pq_planes_t* planes, int batch, int kv_heads, int head_dim, int row_lo, int row_hi,
                            const void* step_state, void* stream);
@@ -746,15 +750,45 @@ int spatten_pq_pack_planes(int dtype, const void* kr_cache, const void* v_cache,
  * above): row `row` of k_cache (optional) / v_cache <- k_new / v_new [B,Hkv,d] (strides new_sb, new_sh), of kr_cache <- k_new
  * rotated at slot position `row` (cos / sin [table_rows, d/2]), and that row of every plane.  With `step_state` the row is
  * (state word 0) - 1 and the rotary row is the state's staged one (cos / sin / row ignored): capturable.  A row >= capacity is
- * not written (step form) / refused (host form).  head_dim 64 / 128, the three bit profiles. */
+ * not written (step form) / refused (host form).  head_dim 64 / 128, the three bit profiles.  With step_state: the ONE shared
+ * state (spatten_kv_append_planes_ragged with stride 0). */
 int spatten_kv_append_planes(int dtype, const void* k_new, const void* v_new, int64_t new_sb, int64_t new_sh, void* k_cache,
                              void* kr_cache, void* v_cache, int64_t kv_sb, int64_t kv_sh, const spatten_pq_planes_t* planes,
                              const void* cos, const void* sin, int table_rows, int batch, int kv_heads, int head_dim, int row,
                              int capacity, const void* step_state, void* stream);
+/* The step form of spatten_kv_append_planes for a RAGGED batch: the arguments of spatten_kv_append_planes, in its order — the
+ * strides of k_new / v_new (new_batch_stride, new_head_stride: its new_sb, new_sh) and of the cache planes (kv_batch_stride,
+ * kv_head_stride: its kv_sb, kv_sh), in elements — plus state_stride directly behind step_state: what spatten_pq_decode_args_t
+ * calls step_state_sb.  `step_state` (required) is an array of `batch` states state_stride BYTES apart (a multiple of 256, >=
+ * spatten_step_state_bytes() and below 2^31, the range of the decode block's field; negative, unaligned or overlapping:
+ * SPATTEN_ERR_INVALID, checked at every batch size).  Unit (b, hkv) appends at row (word 0 of state b) - 1 and rotates with state
+ * b's staged row 1; a row < 0 or >= capacity is not written.  One launch, no host value of a length: capturable.  state_stride == 0:
+ * one shared state — bit for bit what spatten_kv_append_planes(step_state) leaves.  cos / sin / table_rows / row are ignored.  The
+ * quantised-query step (spatten_attn_decode_pq_qint refuses k_new) appends with this call. */
+int spatten_kv_append_planes_ragged(int dtype, const void* k_new, const void* v_new, int64_t new_batch_stride,
+                                    int64_t new_head_stride, void* k_cache, void* kr_cache, void* v_cache, int64_t kv_batch_stride,
+                                    int64_t kv_head_stride, const spatten_pq_planes_t* planes, const void* cos, const void* sin,
+                                    int table_rows, int batch, int kv_heads, int head_dim, int row, int capacity,
+                                    const void* step_state, int64_t state_stride, void* stream);
 /* The decode step over the planes: pass 1 (MSB logits -> stash + msb_logit, softmax, P.V over the quantised V,
  * need_lsb[b*H+h] = max_j prob_j < threshold; RequantDecision.scala:44-72) and the refetch pass for the flagged heads (LSB plane +
  * msb_logit; V again, because the probabilities change).  Arguments as in spatten_decode_args_t; the launch appends nothing.
- * flags bit 0: pass 1 only (measurements). */
+ * flags bit 0: pass 1 only (measurements).
+ *
+ * Ragged batch over the profiled planes (step_state_sb != 0): one step state per sequence, exactly "One state per sequence" of
+ * spatten_decode_args_t.  `step_state` is an array of `batch` states step_state_sb BYTES apart (a multiple of 256, >=
+ * spatten_step_state_bytes(); else SPATTEN_ERR_INVALID, as are a negative stride and a stride without step_state — checked at every
+ * batch size).  Sequence b reads its length (1 <= length_b <= kv_len, the common bound), its query's staged rotary row and its
+ * append slot from state b; with k_new, row length_b - 1 of sequence b's cache planes and of every quantised plane is written.  The
+ * launch is laid out for the bound and streams the bound for every sequence; stash and msb_logit entries [length_b, bound) stay
+ * untouched, plane rows [length_b, bound) must be finite.
+ *   served    spatten_attn_decode_pq — both passes, the compact refetch grid, SPATTEN_PQ_MSB_PASS_ONLY, head_ids, head_abs_acc,
+ *             grouped-query caches in the per-head form, the append inside the MSB pass, every dtype, both head dims, the three
+ *             profiles — and spatten_attn_decode_pq_qint (append beforehand with spatten_kv_append_planes_ragged).
+ *   refused   SPATTEN_ERR_UNSUPPORTED, before anything is launched: spatten_attn_decode_pq_cascade (the fold needs an accumulator
+ *             with a batch axis), spatten_attn_decode_pq_local_v (the select and the gather need per-sequence kept counts) and
+ *             spatten_attn_decode_pq_qint_gqa (the grouped MSB pass reads the shared state).  Follow-ups, like the chained launch.
+ *             The legacy pq_* mode of spatten_attn_decode_args refuses a stride as before. */
 #define SPATTEN_PQ_MSB_PASS_ONLY 1
 typedef struct spatten_pq_decode_args {
   uint32_t struct_size; int32_t dtype;
@@ -767,7 +801,9 @@ typedef struct spatten_pq_decode_args {
   int32_t* need_lsb; float threshold; int32_t flags;
   void* workspace; int32_t workspace_splits;
   int32_t batch, heads, kv_heads, head_dim, kv_len, n_splits, kv_len_layout;
-  const int32_t* head_ids; int32_t n_active_heads; int32_t pad0_;
+  const int32_t* head_ids; int32_t n_active_heads;
+  int32_t step_state_sb;                   /* with step_state: BYTES between the states of consecutive sequences; 0 (what a
+                                              zero-filled block of an older caller holds): one shared state.  See above. */
   float* head_abs_acc;
   const void* step_state;
   /* round 5 — the step's APPEND inside the MSB pass (all NULL / 0: the launch appends nothing, as before): row kv_len - 1

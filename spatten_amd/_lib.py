@@ -117,7 +117,7 @@ class PQDecodeArgs(ctypes.Structure):
         ("workspace", c_void_p), ("workspace_splits", c_int32),
         ("batch", c_int32), ("heads", c_int32), ("kv_heads", c_int32), ("head_dim", c_int32), ("kv_len", c_int32),
         ("n_splits", c_int32), ("kv_len_layout", c_int32),
-        ("head_ids", c_void_p), ("n_active_heads", c_int32), ("pad0_", c_int32),
+        ("head_ids", c_void_p), ("n_active_heads", c_int32), ("step_state_sb", c_int32),
         ("head_abs_acc", c_void_p),
         ("step_state", c_void_p),
         ("k_new", c_void_p), ("v_new", c_void_p), ("new_sb", c_int64), ("new_sh", c_int64),
@@ -250,6 +250,8 @@ def _declare(lib):
     lib.spatten_pq_pack_planes.argtypes = [i, p, p, i64, i64, POINTER(PQPlanesDesc), i, i, i, i, i, p, p]
     lib.spatten_kv_append_planes.restype = c_int
     lib.spatten_kv_append_planes.argtypes = [i, p, p, i64, i64, p, p, p, i64, i64, POINTER(PQPlanesDesc), p, p, i, i, i, i, i, i, p, p]
+    lib.spatten_kv_append_planes_ragged.restype = c_int
+    lib.spatten_kv_append_planes_ragged.argtypes = [i, p, p, i64, i64, p, p, p, i64, i64, POINTER(PQPlanesDesc), p, p, i, i, i, i, i, i, p, i64, p]
     lib.spatten_attn_decode_pq.restype = c_int
     lib.spatten_attn_decode_pq.argtypes = [POINTER(PQDecodeArgs), p]
     lib.spatten_pq_local_v_workspace_bytes.restype = c_size_t

@@ -513,6 +513,12 @@ constexpr size_t kDecodeWsHeader = 256;
 inline size_t decode_cnt_bytes(size_t units) { return (units * 2 * sizeof(unsigned) + 255) / 256 * 256; }
 
 static inline bool ok_dtype(int dt) { return dt == SPATTEN_F32 || dt == SPATTEN_F16 || dt == SPATTEN_BF16; }
+// one step state per sequence (a ragged batch), decode_rows_check's rule: a non-zero stride needs a state, whole 256-byte lines
+// apart, no two states overlapping (0: one shared state)
+static inline bool step_stride_ok(const void* step, int64_t sb, int dtype, int head_dim) {
+  if (sb == 0) return true;
+  return step != nullptr && sb > 0 && sb <= 0x7FFFFFFF && sb % 256 == 0 && (size_t)sb >= spatten_step_state_bytes(dtype, head_dim);
+}
 
 }  // namespace spatten
 

@@ -203,16 +203,24 @@ __global__ __launch_bounds__(256) void pq_pack_planes_kernel(const T* __restrict
 // k / v, its rotation into the shadow (modify_llama.py:95-104) and that row of the profiled planes — bit for bit what
 // kv_append_kernel followed by pq_pack_planes_kernel leave there (the rotated values ARE model-dtype values: rope_pair rounds).
 // The two one-row launches cost 4.8 + 3.5 us per layer-step of BASELINE configs[4] under the graph; this one launch replaces them.
-template <typename T, int D, int KB, int VB>
+// RG (spatten_kv_append_planes_ragged with a non-zero stride): one step state per sequence, step_sb bytes apart — unit (b, hkv) takes
+// its row and its staged rotary row from state b.  Its own instantiation: the shared-state kernel keeps its code.  A group of LPR lanes
+// is one unit, so whole groups still leave together when the units of a wave belong to different sequences.
+template <typename T, int D, int KB, int VB, bool RG = false>
 __global__ __launch_bounds__(64) void kv_append_planes_kernel(const T* __restrict__ k_new, const T* __restrict__ v_new,
                                                               int64_t new_sb, int64_t new_sh, T* __restrict__ kc,
                                                               T* __restrict__ krc, T* __restrict__ vc, int64_t kv_sb,
                                                               int64_t kv_sh, const PlanesDev pl, const T* __restrict__ cos,
                                                               const T* __restrict__ sin, int table_rows, int B, int H,
-                                                              int row_host, int cap, const int32_t* __restrict__ step) {
+                                                              int row_host, int cap, const int32_t* __restrict__ step,
+                                                              int64_t step_sb) {
   constexpr int HALF = D / 2, LPR = D / 16, RPB = 64 / LPR;
   const int lane = threadIdx.x, c = lane % LPR;
   const int unit = blockIdx.x * RPB + lane / LPR;
+  if constexpr (RG) {
+    if (unit >= B * H) return;                             // (before the unit's state is addressed)
+    step = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(step) + (unit / H) * step_sb);
+  }
   const int row = step ? step[0] - 1 : row_host;
   if (unit >= B * H || row < 0 || row >= cap) return;      // (whole LPR-groups leave together)
   const int b = unit / H, h = unit % H;
@@ -342,11 +350,11 @@ extern "C" int spatten_pq_pack_planes(int dtype, const void* kr_cache, const voi
   return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
 }
 
-extern "C" int spatten_kv_append_planes(int dtype, const void* k_new, const void* v_new, int64_t new_sb, int64_t new_sh,
-                                        void* k_cache, void* kr_cache, void* v_cache, int64_t kv_sb, int64_t kv_sh,
-                                        const spatten_pq_planes_t* planes, const void* cos, const void* sin, int table_rows,
-                                        int batch, int kv_heads, int head_dim, int row, int capacity, const void* step_state,
-                                        void* stream) {
+namespace spatten {
+static int kv_append_planes_run(int dtype, const void* k_new, const void* v_new, int64_t new_sb, int64_t new_sh, void* k_cache,
+                                void* kr_cache, void* v_cache, int64_t kv_sb, int64_t kv_sh, const spatten_pq_planes_t* planes,
+                                const void* cos, const void* sin, int table_rows, int batch, int kv_heads, int head_dim, int row,
+                                int capacity, const void* step_state, int64_t step_sb, void* stream) {
   PlanesDev pd;
   if (!k_new || !v_new || !kr_cache || !v_cache || !planes_to_dev(planes, pd) || batch <= 0 || kv_heads <= 0 || capacity <= 0)
     return SPATTEN_ERR_INVALID;
@@ -355,13 +363,19 @@ extern "C" int spatten_kv_append_planes(int dtype, const void* k_new, const void
   if (head_dim != 64 && head_dim != 128) return SPATTEN_ERR_UNSUPPORTED;
   const int kb = planes->key_msb_bits, vb = planes->value_bits;
   if (!pq_profile_supported(kb, vb)) return SPATTEN_ERR_UNSUPPORTED;
+  if (!step_stride_ok(step_state, step_sb, dtype, head_dim)) return SPATTEN_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int rpb = 64 / (head_dim / 16);
   const dim3 grid((unsigned)ceil_div(batch * kv_heads, rpb));
-#define SPATTEN_APL(T, DD, KB, VB)                                                                                            \
-  hipLaunchKernelGGL((kv_append_planes_kernel<T, DD, KB, VB>), grid, dim3(64), 0, st, (const T*)k_new, (const T*)v_new, new_sb, \
+#define SPATTEN_APL_K(K, T)                                                                                                    \
+  hipLaunchKernelGGL(K, grid, dim3(64), 0, st, (const T*)k_new, (const T*)v_new, new_sb,                                        \
                      new_sh, (T*)k_cache, (T*)kr_cache, (T*)v_cache, kv_sb, kv_sh, pd, (const T*)cos, (const T*)sin, table_rows, \
-                     batch, kv_heads, row, capacity, (const int32_t*)step_state)
+                     batch, kv_heads, row, capacity, (const int32_t*)step_state, step_sb)
+#define SPATTEN_APL(T, DD, KB, VB)                                                                         \
+  do {                                                                                                     \
+    if (step_sb != 0) SPATTEN_APL_K((kv_append_planes_kernel<T, DD, KB, VB, true>), T);                    \
+    else SPATTEN_APL_K((kv_append_planes_kernel<T, DD, KB, VB>), T);                                       \
+  } while (0)
 #define SPATTEN_APL_D(T, KB, VB) do { if (head_dim == 128) SPATTEN_APL(T, 128, KB, VB); else SPATTEN_APL(T, 64, KB, VB); } while (0)
 #define SPATTEN_APL_T(KB, VB) do { if (dtype == SPATTEN_BF16) SPATTEN_APL_D(bf16_t, KB, VB); else if (dtype == SPATTEN_F16) SPATTEN_APL_D(f16_t, KB, VB); else SPATTEN_APL_D(float, KB, VB); } while (0)
   if (kb == 4) SPATTEN_APL_T(4, 8);
@@ -370,5 +384,26 @@ extern "C" int spatten_kv_append_planes(int dtype, const void* k_new, const void
 #undef SPATTEN_APL_T
 #undef SPATTEN_APL_D
 #undef SPATTEN_APL
+#undef SPATTEN_APL_K
   return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
+}
+}  // namespace spatten
+
+extern "C" int spatten_kv_append_planes(int dtype, const void* k_new, const void* v_new, int64_t new_sb, int64_t new_sh,
+                                        void* k_cache, void* kr_cache, void* v_cache, int64_t kv_sb, int64_t kv_sh,
+                                        const spatten_pq_planes_t* planes, const void* cos, const void* sin, int table_rows,
+                                        int batch, int kv_heads, int head_dim, int row, int capacity, const void* step_state,
+                                        void* stream) {
+  return kv_append_planes_run(dtype, k_new, v_new, new_sb, new_sh, k_cache, kr_cache, v_cache, kv_sb, kv_sh, planes, cos, sin,
+                              table_rows, batch, kv_heads, head_dim, row, capacity, step_state, 0, stream);
+}
+
+extern "C" int spatten_kv_append_planes_ragged(int dtype, const void* k_new, const void* v_new, int64_t new_sb, int64_t new_sh,
+                                               void* k_cache, void* kr_cache, void* v_cache, int64_t kv_sb, int64_t kv_sh,
+                                               const spatten_pq_planes_t* planes, const void* cos, const void* sin,
+                                               int table_rows, int batch, int kv_heads, int head_dim, int row, int capacity,
+                                               const void* step_state, int64_t step_state_sb, void* stream) {
+  if (!step_state) return SPATTEN_ERR_INVALID;
+  return kv_append_planes_run(dtype, k_new, v_new, new_sb, new_sh, k_cache, kr_cache, v_cache, kv_sb, kv_sh, planes, cos, sin,
+                              table_rows, batch, kv_heads, head_dim, row, capacity, step_state, step_state_sb, stream);
 }

@@ -41,6 +41,7 @@ struct PqvParams {
   const T* q; int64_t q_sb, q_sh;
   PlanesDev pl;
   const T* cos; const T* sin; int table_rows;
+  int step_sb;                                   // bytes between the states of consecutive sequences (RG; in the block's former padding)
   T* out; int64_t out_sb;
   T* scores; int64_t sc_sb, sc_sh;
   float* lse;
@@ -241,9 +242,16 @@ template <int KBITS, int W> __device__ inline int qint_dot(const uint32_t (&w)[W
 //   ended (stream order), so its merger's store needs no argument inside the launch; which split merges does not matter.
 // The MSB pass publishes for every head (the MSB-only statistics, final for a confident head), the refetch pass overwrites the
 // flagged ones: exactly the two stores `lse` sees.
+// RG (ragged batch, spatten_pq_decode_args_t::step_state_sb != 0): one step state per sequence — its own instantiation of the DYN
+// forms, as APP is: every other instantiation keeps its code.  Everything the kernel takes from the state — word 0 (the length),
+// word 3 (the fold forms, which have no RG form) and the two staged rotary rows behind the header that the host bakes into p.cos /
+// p.sin (row 0: the query's, row 1: the appended key's) — moves by b * step_sb bytes: b = blockIdx.z is uniform over the workgroup,
+// so this is scalar address arithmetic in front of the first request.  The length then differs per sequence and with it `owns_new`,
+// `hi`, the stash descriptors and the append's N <= p.N guard; the grid, the workspace and the merges are laid out for the bound.
 template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false, bool QI = false,
-          bool CF = false>
+          bool CF = false, bool RG = false>
 __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams<T> p_in) {
+  static_assert(!RG || (DYN && !SO && !CF), "one state per sequence: the device-length forms of the full step, no fold");
   static_assert(!QI || (sizeof(T) < 4 && KB != 6 && !APP && !SO), "the quantised-query form: 16-bit dtypes, (8, 8) / (4, 8), no append, full P.V");
   static_assert(!CF || (!APP && !SO && !QI), "the cascade form: the full step, no in-launch append, fp32 query");
   PqvParams<T> p = p_in;                         // (the compact refetch pass picks its split layout by the number of flagged heads)
@@ -272,6 +280,12 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
 
   int split = blockIdx.x;
   const int b = blockIdx.z;
+  if constexpr (RG) {
+    const int64_t so = (int64_t)b * p.step_sb;
+    p.step = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p.step) + so);
+    p.cos = reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.cos) + so);
+    p.sin = reinterpret_cast<const T*>(reinterpret_cast<const char*>(p.sin) + so);
+  }
   int y = blockIdx.y;
   if (PASS == 2 && p.compact) {
     int f = 0;
@@ -775,6 +789,10 @@ template <typename K> static int resident_capacity(K kernel) {
 
 template <typename T, int D, int KB, int VB, bool SO = false, bool QI = false, bool CF = false>
 static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st, bool refetch_only = false) {
+  const bool ragged = dyn && p.step_sb != 0;     // (one state per sequence: the RG instantiations)
+  // the fold forms have no RG instantiation: spatten_attn_decode_pq_local_v / _pq_cascade refuse a stride before they get here, and a
+  // caller that did not must not fall through to the shared-state kernels with a strided state
+  if ((SO || CF) && ragged) return SPATTEN_ERR_UNSUPPORTED;
   const bool app = p.k_new != nullptr;
   constexpr int UP = kPqvUp;
   const dim3 grid((unsigned)p.S, (unsigned)n_active, (unsigned)p.B), blk(kPqvThreads);
@@ -784,7 +802,16 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
                                          resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, QI, CF>));
   static const int cap_dyn = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, QI, CF>),
                                       resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, QI, CF>));
-  p.poll_merge = (p.S > 1 && (long long)p.S * n_active * p.B <= (dyn ? cap_dyn : cap_static)) ? 1 : 0;
+  int cap = dyn ? cap_dyn : cap_static;
+  if constexpr (!SO && !CF) {
+    if (ragged) {            // (asked only when a ragged launch arrives: the shared-state forms keep their answers)
+      static const int cap_rg = std::min({resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, QI, false, true>),
+                                          resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, QI, false, true>),
+                                          QI ? 0x7FFFFFFF : resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, !QI, false, QI, false, true>)});
+      cap = cap_rg;
+    }
+  }
+  p.poll_merge = (p.S > 1 && (long long)p.S * n_active * p.B <= cap) ? 1 : 0;
   // ---- the refetch pass (round 6): at the reference traces' rate 2-3 of 30 heads are flagged per layer-step; laid out like pass 1
   // their rows sit on S CUs each and the pass takes as long as if every head were flagged (a CU streams at ~21 B/ns).  So pass 2
   // gets its own, finer split-N (~256-row chunks, <= 64 splits) over a grid whose rows are the RANKS of the flagged heads: a few
@@ -804,7 +831,10 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
   // (SO: the scores-only kernels need no more registers than the full ones — the capacities above stay a safe bound)
   if constexpr (QI) {      // (no append and no scores-only form: spatten_attn_decode_pq_qint refuses them)
     // (refetch_only: the grouped MSB pass of pq_gqa.hip has run in pass 1's place)
-    if (dyn) {
+    if (ragged) {
+      if (!refetch_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, true, false, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, true, false, true>), grid2, blk, 0, st, p2);
+    } else if (dyn) {
       if (!refetch_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, true>), grid, blk, 0, st, p);
       if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, true>), grid2, blk, 0, st, p2);
     } else {
@@ -822,7 +852,13 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
     }
     return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
   } else
-  if (dyn) {
+  if (ragged) {
+    if constexpr (!SO) {
+      if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, true, false, false, false, true>), grid, blk, 0, st, p);
+      else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, false, false, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, false, false, true>), grid2, blk, 0, st, p2);
+    }                      // (SO: refused at the top)
+  } else if (dyn) {
     if (app) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, true, SO>), grid, blk, 0, st, p);
     else hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, SO>), grid, blk, 0, st, p);
     if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, SO>), grid2, blk, 0, st, p2);
@@ -858,6 +894,7 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
   p.pl = pd;
   p.cos = (const T*)a->cos; p.sin = (const T*)a->sin; p.table_rows = a->table_rows;
   p.step = (const int32_t*)a->step_state;
+  p.step_sb = a->step_state ? a->step_state_sb : 0;
   p.pos_q = a->pos_q;
   if (a->step_state) {   // the state's staged rotary rows stand in for the table: row 0 = the query's position
     p.cos = (const T*)((const char*)a->step_state + kStepHeader);
@@ -1107,6 +1144,9 @@ int pq_validate(const spatten_pq_decode_args_t* a, PlanesDev& pd) {
   if (!ok_dtype(a->dtype)) return SPATTEN_ERR_INVALID;
   if (a->head_dim != 64 && a->head_dim != 128) return SPATTEN_ERR_UNSUPPORTED;
   if (!pq_profile_supported(a->planes->key_msb_bits, a->planes->value_bits)) return SPATTEN_ERR_UNSUPPORTED;
+  // one state per sequence (a ragged batch): decode_rows_check's rule — whole 256-byte lines apart, no two states overlapping,
+  // checked at every batch size
+  if (!step_stride_ok(a->step_state, a->step_state_sb, a->dtype, a->head_dim)) return SPATTEN_ERR_INVALID;
   return SPATTEN_OK;
 }
 
@@ -1131,6 +1171,7 @@ extern "C" int spatten_attn_decode_pq_cascade(const spatten_pq_cascade_args_t* c
   if (rc != SPATTEN_OK) return rc;
   if (!ca->importance_acc || !ca->prev_lse || !a->lse || !pd.lg) return SPATTEN_ERR_INVALID;
   if (ca->prev_len < 0 || (!a->step_state && ca->prev_len > a->kv_len)) return SPATTEN_ERR_INVALID;
+  if (a->step_state_sb != 0) return SPATTEN_ERR_UNSUPPORTED;     // one [H, L] accumulator cannot take sequences of different lengths
   if (a->k_new != nullptr) return SPATTEN_ERR_UNSUPPORTED;       // append with spatten_kv_append_planes first
   PqLvExtra ex{ca->importance_acc, ca->acc_sh, ca->prev_lse, ca->prev_len, true};
   if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream, &ex);
@@ -1174,6 +1215,7 @@ extern "C" int spatten_attn_decode_pq_local_v(const spatten_pq_local_v_args_t* l
   PlanesDev pd;
   const int rc = pq_validate(a, pd);
   if (rc != SPATTEN_OK) return rc;
+  if (a->step_state_sb != 0) return SPATTEN_ERR_UNSUPPORTED;     // the select and the gather take ONE kept count from the shared state
   if (a->flags != 0 || !a->scores || !a->lse || !pd.lg || !la->workspace || la->workspace_rows < a->kv_len) return SPATTEN_ERR_INVALID;
   if (a->step_state ? !(la->keep_fraction > 0.0 && la->keep_fraction <= 1.0) : (la->keep <= 0 || !(la->keep_fraction >= 0.0 && la->keep_fraction <= 1.0)))
     return SPATTEN_ERR_INVALID;

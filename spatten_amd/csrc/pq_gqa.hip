@@ -567,6 +567,7 @@ extern "C" int spatten_attn_decode_pq_qint_gqa(const spatten_pq_qint_args_t* qa,
   PlanesDev pd;
   const int rc = pq_validate(a, pd);
   if (rc != SPATTEN_OK) return rc;
+  if (a->step_state_sb != 0) return SPATTEN_ERR_UNSUPPORTED;     // the grouped MSB pass reads the one shared state
   // (the exported query leaves as two 8-byte stores per lane and piece; the query rows are read 16 bytes at a time)
   if (((uintptr_t)qa->q_int | (uintptr_t)qa->qi_sb | (uintptr_t)qa->qi_sh) & 7u) return SPATTEN_ERR_INVALID;
   if (a->k_new != nullptr || a->head_ids != nullptr || a->head_abs_acc != nullptr) return SPATTEN_ERR_UNSUPPORTED;

@@ -1592,7 +1592,11 @@ class PQProfilePlanes:
 def pq_pack_planes(kr_cache: torch.Tensor, v_cache: torch.Tensor, planes: PQProfilePlanes, lo: int, hi: int,
                    step: Optional["StepState"] = None):
     """Quantise rows [lo, hi) of the rotated shadow into the key planes and of the values into the value plane; with
-    ``step`` the one row (state length) - 1 (device-length form: capturable), ``hi`` = the planes' capacity."""
+    ``step`` the one row (state length) - 1 (device-length form: capturable), ``hi`` = the planes' capacity.  The state is the ONE
+    shared state: a ragged batch packs its step rows with ``kv_append_planes(step=...)`` or inside ``attn_decode_pqv(append=...)``."""
+    if step is not None and getattr(step, "batch", None) is not None:
+        raise NotImplementedError("pq_pack_planes(step=...) reads one shared state: a ragged batch (StepState(batch=B)) packs its "
+                                  "step rows with ops.kv_append_planes(step=...) or attn_decode_pqv(append=...)")
     _dev(kr_cache, v_cache, planes.msb)
     B, Hkv, cap, d = kr_cache.shape
     if v_cache.stride() != kr_cache.stride() or kr_cache.stride(3) != 1 or kr_cache.stride(2) != d:
@@ -1610,7 +1614,8 @@ def kv_append_planes(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: Optional
                      step: Optional["StepState"] = None):
     """One decode step's append AND its rows of the profiled planes in one launch (spatten_kv_append_planes): row ``row`` of the
     slab planes from k_new / v_new [B,Hkv,d] — what ``kv_append`` + ``pq_pack_planes(row, row + 1)`` leave, bit for bit; with
-    ``step`` the row (state length) - 1, rotated with the state's staged row (capturable; ``row`` / ``cos`` / ``sin`` unused)."""
+    ``step`` the row (state length) - 1, rotated with the state's staged row (capturable; ``row`` / ``cos`` / ``sin`` unused).
+    ``step = StepState(batch=B)``: sequence b appends at ITS row with its staged row (spatten_kv_append_planes_ragged)."""
     _dev(k_new, v_new, k_cache, kr_cache, v_cache, planes.msb)
     B, Hkv, d = k_new.shape
     if k_new.stride(2) != 1 or v_new.stride() != k_new.stride():
@@ -1621,6 +1626,16 @@ def kv_append_planes(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: Optional
     cap = min(kr_cache.shape[2], planes.capacity)
     if step is None and not (0 <= row < cap and row < cos.shape[0]):
         raise ValueError("append exceeds cache capacity, the planes or the rotary table")
+    if step is not None and getattr(step, "batch", None) is not None:      # one state per sequence (ragged batch)
+        if step.batch != B:
+            raise ValueError(f"step state holds {step.batch} sequences, the append has {B}")
+        rc = _lib.load().spatten_kv_append_planes_ragged(_dt(k_new), k_new.data_ptr(), v_new.data_ptr(), k_new.stride(0),
+                                                         k_new.stride(1), _ptr(k_cache), kr_cache.data_ptr(), v_cache.data_ptr(),
+                                                         kr_cache.stride(0), kr_cache.stride(1), ctypes.byref(planes.desc),
+                                                         cos.data_ptr(), sin.data_ptr(), cos.shape[0], B, Hkv, d, int(row), int(cap),
+                                                         step.data_ptr(), step.stride, _stream())
+        _lib.check(rc, "spatten_kv_append_planes_ragged")
+        return
     rc = _lib.load().spatten_kv_append_planes(_dt(k_new), k_new.data_ptr(), v_new.data_ptr(), k_new.stride(0), k_new.stride(1),
                                               _ptr(k_cache), kr_cache.data_ptr(), v_cache.data_ptr(), kr_cache.stride(0),
                                               kr_cache.stride(1), ctypes.byref(planes.desc), cos.data_ptr(), sin.data_ptr(),
@@ -1653,7 +1668,20 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
     (max, sum) in ``prev_lse``, which this call refreshes) are added to acc for rows < prev_len (with ``step``: state word 3); out,
     stash, lse and need_lsb are the plain step's bit for bit, and ``planes.msb_logit`` holds the logits the output came from
     (flagged heads: the final ones).  ``lse`` is required; no ``append`` (call ``kv_append_planes`` first), no ``query_bits`` /
-    ``grouped``."""
+    ``grouped``.
+    ``step = StepState(batch=B)``: one state per sequence of a ragged batch — sequence b reads its own length (<= ``kv_len``, the
+    common bound), query position and append slot; ``append`` and ``query_bits`` work as with one state, ``cascade`` and
+    ``grouped`` do not (NotImplementedError)."""
+    ragged = step is not None and getattr(step, "batch", None) is not None
+    if ragged:
+        if cascade is not None:
+            raise NotImplementedError("attn_decode_pqv(cascade=...) with one state per sequence: the accumulator [H, L] has no batch "
+                                      "axis, so it cannot take sequences of different lengths")
+        if grouped:
+            raise NotImplementedError("attn_decode_pqv(grouped=True) with one state per sequence: the grouped MSB pass reads the one "
+                                      "shared state — use the per-head form (grouped=False)")
+        if step.batch != q.shape[0]:
+            raise ValueError(f"step state holds {step.batch} sequences, the launch has {q.shape[0]}")
     if cascade is not None:
         if query_bits is not None or grouped:
             raise NotImplementedError("attn_decode_pqv(cascade=...) has no quantised-query / grouped form")
@@ -1721,6 +1749,8 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
         a.head_ids, a.n_active_heads = head_ids.data_ptr(), head_ids.numel()
     a.head_abs_acc = _ptr(head_abs)
     a.step_state = None if step is None else step.data_ptr()
+    if ragged:
+        a.step_state_sb = step.stride
     if append is not None:
         k_new, v_new, k_cache, kr_cache, v_cache = append
         _dev(k_new, v_new, k_cache, kr_cache, v_cache)
@@ -1815,7 +1845,11 @@ def attn_decode_pq_local_v(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int
     host form a ``keep_fraction`` (the one ``keep`` came from) lays the gather out for the layout length, as the step form does.
     ``cascade`` = (acc [H, >=kv_len] fp32, prev_lse [B,H,2] fp32, prev_len): the previous step's probabilities (its final logits
     in ``planes.msb_logit``, its (max, sum) in ``prev_lse``, which this call refreshes) are folded into acc for rows < prev_len
-    (with ``step``: state word 3).  Returns out [B, H*d]; ``need_lsb`` int32 [B*H] is written."""
+    (with ``step``: state word 3).  Returns out [B, H*d]; ``need_lsb`` int32 [B*H] is written.  ``step`` is the ONE shared state
+    (``StepState(batch=B)``: NotImplementedError)."""
+    if step is not None and getattr(step, "batch", None) is not None:
+        raise NotImplementedError("attn_decode_pq_local_v with one state per sequence: the select and the gather take ONE kept count "
+                                  "from the shared state — per-sequence kept counts are not built")
     _dev(q, planes.msb, cos, sin, out, need_lsb, scores, lse, head_ids, head_abs)
     B, H, d = q.shape
     Hkv = planes.msb.shape[1]
