@@ -581,6 +581,8 @@ int spatten_importance_accumulate(int dtype, const void* stash, int64_t sb, int6
  *   acc[b * acc_batch_stride + h * acc_head_stride + j] += exp(s - (m == -inf ? 0 : m)) / l
  * — spatten_importance_accumulate's expression for one row, one add per entry: on sequence b's slice with kv_len = n it leaves the
  * bits that call leaves.  One launch, no host value of a length: capturable.  step_state_sb == 0: one state for the whole batch.
+ * The pending step of spatten_attn_decode_pq_cascade[_ragged] — ONE pair of buffers, the fp32 logits in msb_logit and lse — is flushed
+ * by passing msb_logit / lse as BOTH pairs with SPATTEN_F32: which buffer (cnt - 1) & 1 names is then immaterial.
  * SPATTEN_ERR_INVALID: NULL pointers, batch / heads / bound <= 0, negative strides of acc, acc_batch_stride == 0 with batch > 1, a
  * step_state_sb that is negative or no multiple of 4. */
 int spatten_importance_accumulate_step(int dtype, const void* stash0, const float* lse0, const void* stash1, const float* lse1,
@@ -784,9 +786,11 @@ int spatten_kv_append_planes_ragged(int dtype, const void* k_new, const void* v_
  * untouched, plane rows [length_b, bound) must be finite.
  *   served    spatten_attn_decode_pq — both passes, the compact refetch grid, SPATTEN_PQ_MSB_PASS_ONLY, head_ids, head_abs_acc,
  *             grouped-query caches in the per-head form, the append inside the MSB pass, every dtype, both head dims, the three
- *             profiles — and spatten_attn_decode_pq_qint (append beforehand with spatten_kv_append_planes_ragged).
- *   refused   SPATTEN_ERR_UNSUPPORTED, before anything is launched: spatten_attn_decode_pq_cascade (the fold needs an accumulator
- *             with a batch axis), spatten_attn_decode_pq_local_v (the select and the gather need per-sequence kept counts) and
+ *             profiles —, spatten_attn_decode_pq_qint (append beforehand with spatten_kv_append_planes_ragged) and the cascade step
+ *             in its own entry point, spatten_attn_decode_pq_cascade_ragged (one accumulator per sequence; below).
+ *   refused   SPATTEN_ERR_UNSUPPORTED, before anything is launched: spatten_attn_decode_pq_cascade (its block has no batch stride
+ *             for the accumulator, so the old call still refuses a state stride: spatten_attn_decode_pq_cascade_ragged serves),
+ *             spatten_attn_decode_pq_local_v (the select and the gather need per-sequence kept counts) and
  *             spatten_attn_decode_pq_qint_gqa (the grouped MSB pass reads the shared state).  Follow-ups, like the chained launch.
  *             The legacy pq_* mode of spatten_attn_decode_args refuses a stride as before. */
 #define SPATTEN_PQ_MSB_PASS_ONLY 1
@@ -882,6 +886,27 @@ typedef struct spatten_pq_cascade_args {
   float* prev_lse;
 } spatten_pq_cascade_args_t;
 int spatten_attn_decode_pq_cascade(const spatten_pq_cascade_args_t* args, void* stream);
+/* The cascade step of a RAGGED batch over the planes: spatten_attn_decode_pq_cascade with one step state and one accumulator per
+ * sequence.  `args` is the block spatten_attn_decode_pq_cascade takes, unchanged; args->step.step_state is an array of `batch`
+ * states args->step.step_state_sb BYTES apart ("Ragged batch over the profiled planes": the stride's rule, checked at every batch
+ * size, batch 1 included) and importance_acc is [B, H, >= kv_len] fp32, acc_batch_stride ELEMENTS between the accumulators of
+ * consecutive sequences.  Sequence b, head h, key j adds into importance_acc[b * acc_batch_stride + h * acc_sh + j] for j below the
+ * rows sequence b's OWN previous step wrote (word 3 of state b; 0 after a set: nothing is folded), from the final fp32 logits that
+ * step left in msb_logit[b] and its (max, sum) in prev_lse[b*H+h], by the expression above: exp(old - (m == -inf ? 0 : m)) / l.
+ * Exactly one add per (b, h, j) and step, each into an element of its own: the accumulator has one value at every batch size.
+ * args->prev_len is ignored.  out, the stash, lse, need_lsb, head_abs_acc, the refetch pass and prev_lse on return are the ragged
+ * spatten_attn_decode_pq's bit for bit, msb_logit holds the final logits of flagged heads, and sequence b's slices are bit for bit
+ * what the shared-state call leaves on them at batch 1.  Stash, msb_logit and accumulator entries at or past a sequence's rows and
+ * the rows of unlaunched heads stay untouched.  The launch is laid out for the bound (kv_len) and streams it for every sequence.
+ * The turn's last step is flushed by spatten_importance_accumulate_step (below its declaration: msb_logit and lse as both buffers),
+ * the batch is pruned by spatten_prune_ragged, the planes are repacked by spatten_pq_pack_planes in its host form over the bound
+ * and spatten_step_set_batch takes the new lengths: no host value of a length anywhere in the turn.
+ * SPATTEN_ERR_INVALID (host arithmetic, before anything is launched): whatever spatten_attn_decode_pq_cascade refuses as invalid;
+ * NULL step.step_state; step.step_state_sb == 0 (the shared state stays with spatten_attn_decode_pq_cascade); a bad state stride;
+ * acc_batch_stride < 0.  SPATTEN_ERR_UNSUPPORTED: acc_batch_stride == 0 (the decode block's rule for acc_sb == 0 with a strided
+ * state: one [H, L] accumulator cannot take sequences of different lengths) or >= 2^31 (the range of that field); step.k_new set (append with
+ * spatten_kv_append_planes_ragged first). */
+int spatten_attn_decode_pq_cascade_ragged(const spatten_pq_cascade_args_t* args, int64_t acc_batch_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Quantised query: the decode step over the planes with integer dot products (opt-in; parity unpinned — the RTL multiplies

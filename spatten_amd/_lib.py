@@ -260,6 +260,8 @@ def _declare(lib):
     lib.spatten_attn_decode_pq_local_v.argtypes = [POINTER(PQLocalVArgs), p]
     lib.spatten_attn_decode_pq_cascade.restype = c_int
     lib.spatten_attn_decode_pq_cascade.argtypes = [POINTER(PQCascadeArgs), p]
+    lib.spatten_attn_decode_pq_cascade_ragged.restype = c_int
+    lib.spatten_attn_decode_pq_cascade_ragged.argtypes = [POINTER(PQCascadeArgs), i64, p]
     lib.spatten_attn_decode_pq_qint.restype = c_int
     lib.spatten_attn_decode_pq_qint.argtypes = [POINTER(PQQintArgs), p]
     lib.spatten_pq_qint_supported.restype = c_int

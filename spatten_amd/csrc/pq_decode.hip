@@ -63,7 +63,10 @@ struct PqvParams {
   // the CASCADE form of the full step (CF, spatten_attn_decode_pq_cascade): the same fold inside the full MSB pass; the refetch pass
   // writes the flagged heads' final logits back to msb_logit, and the merging workgroup of either pass publishes the unit's (max, sum)
   // to prev_lse (the kernel comment carries the ordering argument)
-  float* acc; int64_t acc_sh; float* prev_lse; int prev_len;
+  // the RAGGED cascade form (CF && RG, spatten_attn_decode_pq_cascade_ragged): acc_sb = ELEMENTS between the accumulators of
+  // consecutive sequences — 32 bits in the block's padding behind prev_len, like step_sb: the block keeps its size and every field
+  // its offset, so every older instantiation keeps its code down to the offsets of the hidden arguments behind the block
+  float* acc; int64_t acc_sh; float* prev_lse; int prev_len; int acc_sb;
   // the QUANTISED QUERY form (QI, spatten_attn_decode_pq_qint): the rotated query quantised once per head to qmax = 2^(query_bits-1) - 1
   // levels, every key scored with integer dot products; split 0 of the MSB pass exports q_int [B,H,d] (element order) and q_scale [B,H]
   int8_t* qi_out; int64_t qi_sb, qi_sh; float* qs_out; int qmax;
@@ -244,14 +247,22 @@ template <int KBITS, int W> __device__ inline int qint_dot(const uint32_t (&w)[W
 // flagged ones: exactly the two stores `lse` sees.
 // RG (ragged batch, spatten_pq_decode_args_t::step_state_sb != 0): one step state per sequence — its own instantiation of the DYN
 // forms, as APP is: every other instantiation keeps its code.  Everything the kernel takes from the state — word 0 (the length),
-// word 3 (the fold forms, which have no RG form) and the two staged rotary rows behind the header that the host bakes into p.cos /
+// word 3 (the cascade fold's rows; the scores-only fold has no RG form) and the two staged rotary rows behind the header that the host bakes into p.cos /
 // p.sin (row 0: the query's, row 1: the appended key's) — moves by b * step_sb bytes: b = blockIdx.z is uniform over the workgroup,
 // so this is scalar address arithmetic in front of the first request.  The length then differs per sequence and with it `owns_new`,
 // `hi`, the stash descriptors and the append's N <= p.N guard; the grid, the workspace and the merges are laid out for the bound.
+// CF && RG (spatten_attn_decode_pq_cascade_ragged): sequence b folds the rows of ITS previous step (its word 3) into acc + b *
+// acc_sb — still one add per (b, h, j) and step, now into an element no other workgroup adds to (the shared-state form's batch
+// rows meet in one [H, L] accumulator; here they do not), so the result has one value at every batch size.  The ordering argument
+// for prev_lse above is per UNIT and mentions no length: a unit's splits are the same S workgroups whatever its sequence's length
+// is (the grid is laid out for the bound; a split whose chunk lies past length_b scores no row, folds no row — j < hi fails — and
+// still publishes its empty partial behind the same __syncthreads()), each of them loads prev_lse[unit] before its first tile,
+// and the unit's merger stores it only after all S partials carry the tag.  Another sequence's length moves only that sequence's
+// units, whose prev_lse entries are other addresses.
 template <typename T, int D, int KB, int VB, int PASS, bool DYN, int UP, bool APP = false, bool SO = false, bool QI = false,
           bool CF = false, bool RG = false>
 __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams<T> p_in) {
-  static_assert(!RG || (DYN && !SO && !CF), "one state per sequence: the device-length forms of the full step, no fold");
+  static_assert(!RG || (DYN && !SO), "one state per sequence: the device-length forms of the full step (CF: the cascade fold)");
   static_assert(!QI || (sizeof(T) < 4 && KB != 6 && !APP && !SO), "the quantised-query form: 16-bit dtypes, (8, 8) / (4, 8), no append, full P.V");
   static_assert(!CF || (!APP && !SO && !QI), "the cascade form: the full step, no in-launch append, fp32 query");
   PqvParams<T> p = p_in;                         // (the compact refetch pass picks its split layout by the number of flagged heads)
@@ -458,6 +469,7 @@ __global__ __launch_bounds__(kPqvThreads) void pqv_decode_kernel(const PqvParams
   const __amdgpu_buffer_rsrc_t rs_lgw = make_rsrc(lgb, (PASS == 1 || SO || CF) ? (int64_t)hi * 4 : 0);
   const int prev_len = !fold ? 0 : (p.acc == nullptr) ? 0 : DYN ? __builtin_amdgcn_readfirstlane(pl_dyn) : p.prev_len;
   float* accp = (fold && p.acc != nullptr) ? p.acc + h * p.acc_sh : nullptr;
+  if constexpr (CF && RG) { if (accp) accp += (int64_t)b * p.acc_sb; }
   // (exp / sum with a true division: the same bits as spatten_importance_accumulate's fold of the same row, so a step folded
   //  here and a step folded by the flush add identical values — an eager loop and a graph that binds mid-turn agree)
   const float casc_m = (prev_ml[0] == -INFINITY) ? 0.f : prev_ml[0], casc_l = prev_ml[1];
@@ -788,11 +800,14 @@ template <typename K> static int resident_capacity(K kernel) {
 }
 
 template <typename T, int D, int KB, int VB, bool SO = false, bool QI = false, bool CF = false>
-static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st, bool refetch_only = false) {
+static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hipStream_t st, bool refetch_only = false,
+                      bool cascade_ragged = false) {
   const bool ragged = dyn && p.step_sb != 0;     // (one state per sequence: the RG instantiations)
-  // the fold forms have no RG instantiation: spatten_attn_decode_pq_local_v / _pq_cascade refuse a stride before they get here, and a
-  // caller that did not must not fall through to the shared-state kernels with a strided state
-  if ((SO || CF) && ragged) return SPATTEN_ERR_UNSUPPORTED;
+  // the scores-only fold has no RG instantiation and the cascade fold's is reached from spatten_attn_decode_pq_cascade_ragged alone:
+  // spatten_attn_decode_pq_local_v / _pq_cascade refuse a stride before they get here, and a caller that did not must not fall
+  // through to the shared-state kernels with a strided state
+  if ((SO || CF) && ragged && !(CF && cascade_ragged)) return SPATTEN_ERR_UNSUPPORTED;
+  if (cascade_ragged && !(CF && ragged)) return SPATTEN_ERR_INVALID;
   const bool app = p.k_new != nullptr;
   constexpr int UP = kPqvUp;
   const dim3 grid((unsigned)p.S, (unsigned)n_active, (unsigned)p.B), blk(kPqvThreads);
@@ -809,6 +824,13 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
                                           resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, QI, false, true>),
                                           QI ? 0x7FFFFFFF : resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, !QI, false, QI, false, true>)});
       cap = cap_rg;
+    }
+  }
+  if constexpr (CF) {
+    if (ragged) {            // (likewise: asked when the first ragged cascade launch arrives)
+      static const int cap_cf_rg = std::min(resident_capacity(pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, false, true, true>),
+                                            resident_capacity(pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, false, true, true>));
+      cap = cap_cf_rg;
     }
   }
   p.poll_merge = (p.S > 1 && (long long)p.S * n_active * p.B <= cap) ? 1 : 0;
@@ -842,8 +864,11 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
       if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, false, UP, false, false, true>), grid2, blk, 0, st, p2);
     }
     return hipGetLastError() == hipSuccess ? SPATTEN_OK : SPATTEN_ERR_LAUNCH;
-  } else if constexpr (CF) {   // (no append: spatten_attn_decode_pq_cascade refuses it)
-    if (dyn) {
+  } else if constexpr (CF) {   // (no append: spatten_attn_decode_pq_cascade[_ragged] refuse it)
+    if (ragged) {
+      hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, false, true, true>), grid, blk, 0, st, p);
+      if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, false, true, true>), grid2, blk, 0, st, p2);
+    } else if (dyn) {
       hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 1, true, UP, false, false, false, true>), grid, blk, 0, st, p);
       if (!msb_only) hipLaunchKernelGGL((pqv_decode_kernel<T, D, KB, VB, 2, true, UP, false, false, false, true>), grid2, blk, 0, st, p2);
     } else {
@@ -872,7 +897,8 @@ static int launch_pqv(PqvParams<T>& p, int n_active, bool dyn, bool msb_only, hi
 
 // the local-V extras of spatten_attn_decode_pq_local_v (NULL: the plain profiled step); full: spatten_attn_decode_pq_cascade — the
 // fold inside the FULL step (the CF instantiations) instead of the scores-only passes
-struct PqLvExtra { float* acc; int64_t acc_sh; float* prev_lse; int prev_len; bool full; };
+// acc_sb != 0: spatten_attn_decode_pq_cascade_ragged — one accumulator per sequence (the CF && RG instantiations)
+struct PqLvExtra { float* acc; int64_t acc_sh; float* prev_lse; int prev_len; bool full; int64_t acc_sb = 0; };
 
 template <typename T>
 static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipStream_t st, const PqLvExtra* lv = nullptr,
@@ -916,7 +942,7 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
   p.k_new = (const T*)a->k_new; p.v_new = (const T*)a->v_new; p.new_sb = a->new_sb; p.new_sh = a->new_sh;
   p.kc = (T*)a->k_cache; p.krc = (T*)a->kr_cache; p.vc = (T*)a->v_cache; p.kv_sb = a->kv_sb; p.kv_sh = a->kv_sh;
   p.nr_row = a->step_state ? 1 : std::min(a->kv_len - 1, a->table_rows - 1);
-  p.acc = lv ? lv->acc : nullptr; p.acc_sh = lv ? lv->acc_sh : 0;
+  p.acc = lv ? lv->acc : nullptr; p.acc_sh = lv ? lv->acc_sh : 0; p.acc_sb = lv ? (int)lv->acc_sb : 0;
   p.prev_lse = (lv && lv->acc) ? lv->prev_lse : a->lse; p.prev_len = (lv && lv->acc) ? lv->prev_len : 0;
   p.qi_out = qx ? qx->q_int : nullptr; p.qi_sb = qx ? qx->qi_sb : 0; p.qi_sh = qx ? qx->qi_sh : 0;
   p.qs_out = qx ? qx->q_scale : nullptr; p.qmax = qx ? qx->qmax : 0;
@@ -926,7 +952,7 @@ static int run_pqv(const spatten_pq_decode_args_t* a, const PlanesDev& pd, hipSt
     if constexpr (sizeof(T) < 4 && KB != 6) {                                                       \
       if (qx) return launch_pqv<T, DD, KB, VB, false, true>(p, n_active, dyn, msb_only, st, refetch_only); \
     }                                                                                               \
-    if (lv && lv->full) return launch_pqv<T, DD, KB, VB, false, false, true>(p, n_active, dyn, msb_only, st); \
+    if (lv && lv->full) return launch_pqv<T, DD, KB, VB, false, false, true>(p, n_active, dyn, msb_only, st, false, lv->acc_sb != 0); \
     return lv ? launch_pqv<T, DD, KB, VB, true>(p, n_active, dyn, msb_only, st)                     \
               : launch_pqv<T, DD, KB, VB>(p, n_active, dyn, msb_only, st);                          \
   } while (0)
@@ -1174,6 +1200,24 @@ extern "C" int spatten_attn_decode_pq_cascade(const spatten_pq_cascade_args_t* c
   if (a->step_state_sb != 0) return SPATTEN_ERR_UNSUPPORTED;     // one [H, L] accumulator cannot take sequences of different lengths
   if (a->k_new != nullptr) return SPATTEN_ERR_UNSUPPORTED;       // append with spatten_kv_append_planes first
   PqLvExtra ex{ca->importance_acc, ca->acc_sh, ca->prev_lse, ca->prev_len, true};
+  if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream, &ex);
+  if (a->dtype == SPATTEN_F16) return run_pqv<f16_t>(a, pd, (hipStream_t)stream, &ex);
+  return run_pqv<float>(a, pd, (hipStream_t)stream, &ex);
+}
+
+extern "C" int spatten_attn_decode_pq_cascade_ragged(const spatten_pq_cascade_args_t* ca, int64_t acc_batch_stride, void* stream) {
+  if (!ca || ca->struct_size != sizeof(spatten_pq_cascade_args_t)) return SPATTEN_ERR_INVALID;
+  const spatten_pq_decode_args_t* a = &ca->step;
+  PlanesDev pd;
+  const int rc = pq_validate(a, pd);                             // (the state stride's rule, at every batch size)
+  if (rc != SPATTEN_OK) return rc;
+  if (!ca->importance_acc || !ca->prev_lse || !a->lse || !pd.lg) return SPATTEN_ERR_INVALID;
+  if (!a->step_state || a->step_state_sb == 0) return SPATTEN_ERR_INVALID;   // the shared state: spatten_attn_decode_pq_cascade
+  if (acc_batch_stride < 0) return SPATTEN_ERR_INVALID;
+  if (acc_batch_stride == 0) return SPATTEN_ERR_UNSUPPORTED;     // one [H, L] accumulator cannot take sequences of different lengths
+  if (acc_batch_stride > 0x7FFFFFFF) return SPATTEN_ERR_UNSUPPORTED;   // (elements; the range of spatten_decode_args_t's acc_sb)
+  if (a->k_new != nullptr) return SPATTEN_ERR_UNSUPPORTED;       // append with spatten_kv_append_planes_ragged first
+  PqLvExtra ex{ca->importance_acc, ca->acc_sh, ca->prev_lse, 0, true, acc_batch_stride};   // (prev_len: every state's word 3)
   if (a->dtype == SPATTEN_BF16) return run_pqv<bf16_t>(a, pd, (hipStream_t)stream, &ex);
   if (a->dtype == SPATTEN_F16) return run_pqv<f16_t>(a, pd, (hipStream_t)stream, &ex);
   return run_pqv<float>(a, pd, (hipStream_t)stream, &ex);

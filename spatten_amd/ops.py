@@ -1290,7 +1290,9 @@ def importance_accumulate_step(acc: torch.Tensor, scores: torch.Tensor, lse: tor
                                prev_lse: torch.Tensor, step: "StepState", bound: int):
     """Fold the PENDING step of a device-length batch (spatten_importance_accumulate_step): ``scores`` / ``lse`` and ``prev_scores`` /
     ``prev_lse`` are the two swapping buffers in the order ``attn_decode`` takes them; each sequence's state says which one its last
-    step wrote and how many rows.  acc fp32 [B, H, >=bound] (or [H, >=bound] at B = 1).  One launch, capturable."""
+    step wrote and how many rows.  acc fp32 [B, H, >=bound] (or [H, >=bound] at B = 1).  One launch, capturable.
+    The cascade step over the profiled planes (``attn_decode_pqv(cascade=...)``) keeps ONE pair of buffers: pass the fp32 logits
+    ``planes.msb_logit`` and ``lse`` as both pairs — which of the two the state names is then immaterial."""
     _dev(acc, scores, lse, prev_scores, prev_lse)
     B, H = scores.shape[0], scores.shape[1]
     if acc.dim() == 2:
@@ -1670,13 +1672,20 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
     (flagged heads: the final ones).  ``lse`` is required; no ``append`` (call ``kv_append_planes`` first), no ``query_bits`` /
     ``grouped``.
     ``step = StepState(batch=B)``: one state per sequence of a ragged batch — sequence b reads its own length (<= ``kv_len``, the
-    common bound), query position and append slot; ``append`` and ``query_bits`` work as with one state, ``cascade`` and
-    ``grouped`` do not (NotImplementedError)."""
+    common bound), query position and append slot; ``append`` and ``query_bits`` work as with one state, ``grouped`` does not
+    (NotImplementedError).  ``cascade`` then takes one accumulator per sequence, acc fp32 [B, H, >=kv_len] with contiguous rows
+    (spatten_attn_decode_pq_cascade_ragged): sequence b folds the rows its own previous step wrote (word 3 of its state) into
+    acc[b], one add per entry, and its slices are bit for bit what the one-state call leaves at batch 1; the third element of the
+    tuple is ignored.  A 2-D acc [H, L] has no batch axis and cannot take sequences of different lengths (NotImplementedError); a
+    3-D acc of another batch or shape is a ValueError.  The turn's last step is flushed with
+    ``importance_accumulate_step(acc, planes.msb_logit, lse, planes.msb_logit, lse, step, bound)``."""
     ragged = step is not None and getattr(step, "batch", None) is not None
     if ragged:
-        if cascade is not None:
+        if cascade is not None and (cascade[0] is None or cascade[0].dim() != 3):
             raise NotImplementedError("attn_decode_pqv(cascade=...) with one state per sequence: the accumulator [H, L] has no batch "
-                                      "axis, so it cannot take sequences of different lengths")
+                                      "axis, so it cannot take sequences of different lengths — pass acc [B, H, L]")
+        if cascade is not None and cascade[0].shape[0] != step.batch:
+            raise ValueError(f"cascade: acc holds {cascade[0].shape[0]} sequences, the step state {step.batch}")
         if grouped:
             raise NotImplementedError("attn_decode_pqv(grouped=True) with one state per sequence: the grouped MSB pass reads the one "
                                       "shared state — use the per-head form (grouped=False)")
@@ -1783,14 +1792,24 @@ def attn_decode_pqv(q: torch.Tensor, planes: PQProfilePlanes, kv_len: int, cos: 
     if cascade is not None:
         acc, prev_lse, prev_len = cascade
         _dev(acc, prev_lse)
-        if acc.dtype != torch.float32 or acc.dim() != 2 or acc.stride(1) != 1 or acc.shape[0] != H or acc.shape[1] < kv_len \
-                or prev_lse.dtype != torch.float32 or prev_lse.numel() != B * H * 2 or not prev_lse.is_contiguous():
+        if ragged:
+            if acc.dtype != torch.float32 or acc.shape[:2] != (B, H) or acc.stride(2) != 1 or acc.shape[2] < kv_len \
+                    or acc.stride(0) <= 0:
+                raise ValueError("cascade with one state per sequence: acc [B, H, >=kv_len] fp32 with contiguous rows")
+        elif acc.dtype != torch.float32 or acc.dim() != 2 or acc.stride(1) != 1 or acc.shape[0] != H or acc.shape[1] < kv_len:
+            raise ValueError("cascade: acc [H, >=kv_len] fp32 with contiguous rows, prev_lse [B,H,2] fp32 contiguous")
+        if prev_lse.dtype != torch.float32 or prev_lse.numel() != B * H * 2 or not prev_lse.is_contiguous():
             raise ValueError("cascade: acc [H, >=kv_len] fp32 with contiguous rows, prev_lse [B,H,2] fp32 contiguous")
         if lse.dtype != torch.float32 or lse.numel() != B * H * 2 or not lse.is_contiguous():
             raise ValueError("cascade: lse [B,H,2] fp32 contiguous")
         ca = _lib.PQCascadeArgs()
-        ca.struct_size, ca.prev_len = ctypes.sizeof(_lib.PQCascadeArgs), int(prev_len)
+        ca.struct_size, ca.prev_len = ctypes.sizeof(_lib.PQCascadeArgs), 0 if ragged else int(prev_len)
         ca.step = a
+        if ragged:
+            ca.importance_acc, ca.acc_sh, ca.prev_lse = acc.data_ptr(), acc.stride(1), prev_lse.data_ptr()
+            _lib.check(_lib.load().spatten_attn_decode_pq_cascade_ragged(ctypes.byref(ca), acc.stride(0), stream),
+                       "spatten_attn_decode_pq_cascade_ragged")
+            return out
         ca.importance_acc, ca.acc_sh, ca.prev_lse = acc.data_ptr(), acc.stride(0), prev_lse.data_ptr()
         _lib.check(_lib.load().spatten_attn_decode_pq_cascade(ctypes.byref(ca), stream), "spatten_attn_decode_pq_cascade")
         return out
